@@ -14,6 +14,12 @@ scaling: fixed work per step).  Rank 0 prints one JSON line.
 
 Run: python bench.py [--gpus N --steps K --warmup W]
      torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full
+adds everything else the bench measures (CPU baselines, the other configs as
+side_configs, --exact's comparison with the default build; N > 1: the C4 line
+and the in-process lines).  --dump-outputs DIR writes what the last timed step
+computed (dump_table) so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -185,6 +191,64 @@ def pmc_traffic(args, kernel, config=None, key=None):
         return None
 
 
+DUMP_MAX_BYTES = 64 * 1000 * 1000   # --dump-outputs: every file of one run together
+DUMP_SAMPLE = 1 << 20               # entries of an output written as a sample
+
+
+def write_outputs(dirpath: str, arrays: dict) -> None:
+    """--dump-outputs: every array as DIR/<name>.npy, f32 or f64 (integers as f64:
+    exact below 2^53), DUMP_MAX_BYTES in all."""
+    os.makedirs(dirpath, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        total += a.nbytes
+        assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes at {name}"
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+    print(f"[bench] outputs: {', '.join(arrays)} ({total} bytes) in {dirpath}", file=sys.stderr, flush=True)
+
+
+def dump_table(dirpath, att, lr, nx, hp, slots, records_everywhere, dev, seed=11):
+    """What the timed path left in the caller's buffers after its last step, read
+    back entry by entry (SB64, include/spe.h: element (s, t) of a span that starts
+    at block b0 lies at ((s / 64 - b0) A + t) 64 + s % 64): `lat` / `rel` from the
+    record span, `next` / `hops` from this rank's packed blocks (`slots`: (b0, b1,
+    first slot) of every span it builds).  NaN where this rank holds no value: next
+    hops of a block another rank keeps, records of a block it neither built nor
+    gathered.  A table of at most DUMP_SAMPLE entries is written whole (row-major),
+    a larger one as DUMP_SAMPLE (source slot, target slot) pairs drawn by numpy's
+    default_rng(seed), the same pairs in every run; `pairs` holds each entry's
+    (source vertex, target vertex)."""
+    import torch
+    A = int(att.shape[0])
+    nblk = (A + 63) // 64
+    if A * A <= DUMP_SAMPLE:
+        s, t = (x.reshape(-1).astype(np.int64) for x in np.meshgrid(np.arange(A), np.arange(A), indexing="ij"))
+    else:
+        p = np.random.default_rng(seed).integers(0, A, size=(DUMP_SAMPLE, 2), dtype=np.int64)
+        s, t = p[:, 0], p[:, 1]
+    slot = np.full(nblk, -1, np.int64)
+    for b0, b1, s0 in slots:
+        slot[b0:b1] = s0 + np.arange(b1 - b0)
+    blk = s // 64
+    own = slot[blk] >= 0
+    rec = (blk * A + t) * 64 + s % 64
+    loc = (np.where(own, slot[blk], 0) * A + t) * 64 + s % 64
+    assert rec.min() >= 0 and rec.max() < lr.shape[0] and loc.min() >= 0 and loc.max() < nx.shape[0] <= hp.shape[0]
+    latrel = lr[torch.from_numpy(rec).to(dev)].cpu().numpy()
+    loc_d = torch.from_numpy(loc).to(dev)
+    nxt = nx[loc_d].cpu().numpy().astype(np.float64)
+    hops = (hp[loc_d].to(torch.int32) & 0xFFFF).cpu().numpy().astype(np.float32)   # u16 kept in an i16 tensor
+    nxt[~own] = np.nan
+    hops[~own] = np.nan
+    if not records_everywhere:
+        latrel[~own] = np.nan
+    write_outputs(dirpath, {"pairs": np.stack([att[s], att[t]], axis=1), "lat": latrel[:, 0], "rel": latrel[:, 1],
+                            "next": nxt, "hops": hops})
+
+
 def bench_lookup(args, rank=0, world=1, local=0, dist=None):
     """C5: batched per-packet lookups (s_slot, t_slot) -> (latency, reliability, ok)
     against the HBM-resident C3 table; 41 algorithmic bytes per query.  N > 1:
@@ -241,6 +305,13 @@ def bench_lookup(args, rank=0, world=1, local=0, dist=None):
         el = float(x.item())
     if rank != 0:
         return
+    if args.dump_outputs:   # a fixed sample of the last step's answers, with the queries they answer
+        pick = (np.arange(q, dtype=np.int64) if q <= DUMP_SAMPLE else
+                np.sort(np.random.default_rng(11).integers(0, q, size=DUMP_SAMPLE, dtype=np.int64)))
+        pick_d = torch.from_numpy(pick).to(dev)
+        write_outputs(args.dump_outputs, {"pairs": pairs[pick_d].cpu().numpy(), "lat": lat[pick_d].cpu().numpy(),
+                                          "rel": rel[pick_d].cpu().numpy(),
+                                          "ok": ok[pick_d].cpu().numpy().astype(np.float32)})
     c5name = "c5" if args.c5_table == "c3" else "c5_on_c4"
     value = world * q * steps / el
     ach = 41.0 * q / kern_s / 1e9
@@ -786,6 +857,8 @@ def bench_table(args, rank, world, local, dist, config=None, replica_only=False)
     torch.cuda.synchronize(dev)
     barrier()
     el = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0 and config == args.config:
+        dump_table(args.dump_outputs, att, lr, nx, hp, slots, not emulated and (world == 1 or gather), dev)
     kp = t.kernel_profile() if not args.no_profile else None
     per_rank = None
     if dist is not None:
@@ -947,8 +1020,8 @@ def default_vs_exact(config: str, parts: int = 0):
     return tot
 
 
-# The default run (C3 at N = 1) also measures BASELINE's other configurations
-# (and C2 on the FW engine),
+# The default config's --full run (C3 at N = 1) also measures BASELINE's other
+# configurations (and C2 on the FW engine),
 # each in a child process of its own once the C3 table is freed (C4's table alone
 # is 220 GB), so that every config has a line on the driver's box.  A child that
 # fails is recorded with its exit status and the tail of its output; the C3 line
@@ -1186,7 +1259,7 @@ def side_configs(timeout_s: float = 240.0):
     for name, argv in SIDE_CONFIGS:
         t0 = time.perf_counter()
         try:
-            r = subprocess.run([sys.executable, "-u", os.path.abspath(__file__), "--no-side"] + argv, env=env,
+            r = subprocess.run([sys.executable, "-u", os.path.abspath(__file__), "--full", "--no-side"] + argv, env=env,
                                cwd=ROOT, capture_output=True, text=True, timeout=timeout_s)
             lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
             if r.returncode == 0 and lines:
@@ -1274,12 +1347,25 @@ def main():
     ap.add_argument("--shares", type=int, default=1, help="emulate one rank of a job with this many GPUs")
     ap.add_argument("--share-index", type=int, default=0, help="--shares: the rank whose chunks this run builds")
     ap.add_argument("--no-side", action="store_true",
-                    help="default C3 run at N = 1: skip the C1/C2/C4/C5 lines measured in child processes")
+                    help="--full C3 run at N = 1: skip the C1/C2/C4/C5 lines measured in child processes")
     ap.add_argument("--inproc", type=int, default=0,
                     help="N > 1: one process over devices 0..N-1 (spe_table_opts.devices) instead of N ranks")
     ap.add_argument("--no-inproc", action="store_true",
                     help="N > 1 without torchrun: skip the in-process multi-device lines after the ranks")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baselines, the other "
+                         "configs as side_configs (N > 1: the C4 line in the same ranks and the in-process "
+                         "lines), --exact's comparison with the default build.  Off: set up, warm up, time "
+                         "the steps, print the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy "
+                         "(f32 / f64, a fixed seeded sample of the table: see dump_table)")
     args = ap.parse_args()
+    if not args.full:   # a plain run: only what the line's own figure needs
+        args.no_cpu_baseline = args.no_side = args.no_compare = args.no_north_star = args.no_inproc = True
+    if args.dump_outputs and (args.inproc > 0 or args.config in ("complete", "c2fw", "c3shim", "c4shim")):
+        raise SystemExit(f"bench.py: --dump-outputs covers the table configs (c1-c4) and c5, not {args.config}"
+                         + (" --inproc" if args.inproc > 0 else ""))
     if args.config == "complete":
         return bench_complete(args)
     if args.config == "c2fw":

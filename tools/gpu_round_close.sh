@@ -1,7 +1,8 @@
-# Round close-out on one GPU: the full GPU suite, then the default bench line
-# (C3 plus every other config's line under side_configs).
+# Round close-out on one GPU: the full GPU suite, then the default config's --full
+# bench line (C3 plus every other config's line under side_configs).
 set -e
-mkdir -p gpurun_out/${ROUND:-r04}
+O=${OUT:-bench_out}/${ROUND:-r04}
+mkdir -p $O
 TAG=${ROUND:-r04}_tests bash tools/gpu_tests.sh
-timeout -k 10 600 python -u bench.py > gpurun_out/${ROUND:-r04}/bench_default.log 2>&1
-tail -c 300 gpurun_out/${ROUND:-r04}/bench_default.log
+timeout -k 10 600 python -u bench.py --full > $O/bench_default.log 2>&1
+tail -c 300 $O/bench_default.log
