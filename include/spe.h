@@ -406,7 +406,8 @@ int spe_table_download_aux(const spe_table* t, int32_t row_begin, int32_t row_en
 /* Batched per-packet lookups against the HBM-resident table.  d_pairs holds q
  * (s_slot, t_slot) int32 pairs; outputs are device arrays of q elements.
  * ok = 1 when routable (topology_isRoutable).  Pairs whose source row is not
- * owned by this table return ok = 0, latency = reliability = -1. */
+ * owned by this table, and pairs with a slot outside [0, n_attached), return
+ * ok = 0, latency = reliability = -1. */
 int spe_lookup_batch(const spe_table* t, const int32_t* d_pairs, int64_t q, double* d_latency,
                      double* d_reliability, uint8_t* d_ok, void* stream);
 /* The same against replica `replica` of a multi-device table (0 = the home
@@ -419,7 +420,7 @@ int spe_lookup_batch_replica(const spe_table* t, int32_t replica, const int32_t*
 int spe_table_replica_device(const spe_table* t, int32_t replica, int32_t* device);
 /* spe_lookup_batch with HOST arrays (pairs: q (s_slot, t_slot) int32 pairs): the
  * batch is staged through pinned buffers to the home replica and answered there,
- * in chunks of 4M queries, synchronously.  For a host caller (the topology shim's
+ * in chunks of 2^21 (2M) queries, synchronously.  For a host caller (the topology shim's
  * topology_getPathInfoBatch) that resolves a round of packets at once instead of
  * one device read per query.  Thread-safe (callers are serialised per table). */
 int spe_lookup_batch_host(const spe_table* t, const int32_t* pairs, int64_t q, double* latency,

@@ -762,7 +762,9 @@ __global__ __launch_bounds__(BLOCK) void k_lookup(const int2* __restrict__ pairs
         const int2 p = pairs[i];
         const int32_t sb = p.x >> 6;
         double L = -1.0, R = -1.0;
-        if (p.x >= 0 && p.y >= 0 && p.y < tb.A && sb >= blk0 && sb < blk1) {
+        // p.x < A: the lanes of the last block past A are padding (no source), and on
+        // caller-owned or gathered storage they hold whatever the caller left there
+        if (p.x >= 0 && p.x < tb.A && p.y >= 0 && p.y < tb.A && sb >= blk0 && sb < blk1) {
             const size_t o = tidx(sb - blk0, tb.A, p.y, p.x & (WAVE - 1));
             if constexpr (NT) {   // no L2 allocation for a record that is never re-read
                 const dvec2 e = __builtin_nontemporal_load(reinterpret_cast<const dvec2*>(tb.lr + o));

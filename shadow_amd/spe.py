@@ -175,6 +175,7 @@ def lib():
         L.spe_table_layout_get.argtypes = [P, P]
         L.spe_table_get.argtypes = [P, C.c_int32, C.c_int32, P]
         L.spe_table_get_latrel.argtypes = [P, C.c_int32, C.c_int32, P, P]
+        L.spe_table_get_row_latrel.argtypes = [P, C.c_int32, P, P]
         L.spe_table_download.argtypes = [P, C.c_int32, C.c_int32, P, P, P, P]
         L.spe_lookup_batch.argtypes = [P, P, C.c_int64, P, P, P, P]
         L.spe_lookup_batch_replica.argtypes = [P, C.c_int32, P, C.c_int64, P, P, P, P]
@@ -413,6 +414,13 @@ class PathTable:
         _check(lib().spe_table_get_latrel(self.h, int(s_slot), int(t_slot), C.byref(lat), C.byref(rel)),
                "spe_table_get_latrel")
         return lat.value, rel.value
+
+    def get_row_latrel(self, s_slot: int):
+        """spe_table_get_row_latrel: (latency[A], reliability[A]) of one source row."""
+        lat = np.empty(self.A, np.float64)
+        rel = np.empty(self.A, np.float64)
+        _check(lib().spe_table_get_row_latrel(self.h, int(s_slot), _p(lat), _p(rel)), "spe_table_get_row_latrel")
+        return lat, rel
 
     def download(self, row_begin: int = 0, row_end: Optional[int] = None,
                  fields=("lat", "rel", "next", "hops")) -> dict:

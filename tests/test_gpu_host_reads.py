@@ -57,6 +57,89 @@ def test_single_entries_equal_the_download(spe, mode, monkeypatch):
     t.close()
 
 
+def _read_entries(t, pairs):
+    """(latency, reliability, next, hops) through spe_table_get and (latency,
+    reliability) through spe_table_get_latrel, for every pair."""
+    full = np.array([[e["latency"], e["reliability"], e["next_hop"], e["hops"]]
+                     for e in (t.get(int(s), int(u)) for s, u in pairs)])
+    latrel = np.array([t.get_latrel(int(s), int(u)) for s, u in pairs])
+    return full, latrel
+
+
+def _assert_entries(got, ref, pairs, what):
+    full, latrel = got
+    s, u = pairs[:, 0], pairs[:, 1]
+    for i, k in enumerate(("lat", "rel", "next", "hops")):
+        exp = ref[k][s, u].astype(np.float64)
+        bad = np.nonzero(full[:, i] != exp)[0]
+        assert bad.size == 0, (f"{what}: spe_table_get {k} differs at {bad.size} of {len(pairs)} entries, first "
+                               f"{pairs[bad[0]].tolist()}: read {full[bad[0], i]!r}, the table holds {exp[bad[0]]!r}")
+    for i, k in enumerate(("lat", "rel")):
+        bad = np.nonzero(latrel[:, i] != ref[k][s, u])[0]
+        assert bad.size == 0, (f"{what}: spe_table_get_latrel {k} differs at {bad.size} entries, first "
+                               f"{pairs[bad[0]].tolist()}: read {latrel[bad[0], i]!r}, the table holds {ref[k][s, u][bad[0]]!r}")
+
+
+@pytest.mark.parametrize("mode", ["auto", "copies"])
+def test_reads_follow_a_rebuild_and_device_writes(spe, mode, monkeypatch):
+    """Single-entry reads are never stale.  Two graphs of one shape, the second with
+    every latency x 1.5, build into the SAME caller-owned tensors: after the first
+    table's reads have decided host_reads, the second build rewrites every record and
+    the first table's reads must return the new ones at once; then torch overwrites
+    100 records on the device and both that table and a table adopted afterwards
+    (ext_filled) must read them.  (The rebuild of test_single_entries_equal_the_download
+    writes the values the table already held, so it could not tell.)"""
+    import math
+    import torch
+    from dataclasses import replace
+    if mode == "copies":
+        monkeypatch.setenv("SPE_HOST_READS", "0")
+    top1 = graphs.gen_random_small(700, 2100, 15)
+    top2 = replace(top1, elat=top1.elat * 1.5)
+    A = np.arange(top1.n, dtype=np.int32)
+    elems = math.ceil(top1.n / 64) * top1.n * 64
+    bufs = [torch.empty((elems, 2), dtype=torch.float64, device="cuda"),
+            torch.empty(elems, dtype=torch.int32, device="cuda"),
+            torch.empty(elems, dtype=torch.int16, device="cuda")]
+    ptrs = [b.data_ptr() for b in bufs]
+    g1, g2 = spe.Graph(top1), spe.Graph(top2)
+    t1 = spe.PathTable(g1, A, ext=ptrs)
+    t2 = spe.PathTable(g2, A, ext=ptrs)
+    rng = np.random.default_rng(6)
+    pairs = rng.integers(0, t1.A, (500, 2))
+    t1.build()
+    got = _read_entries(t1, pairs)          # decides host_reads
+    hr = t1.layout()["host_reads"]
+    print(f"mode {mode}: host_reads={hr}")
+    assert hr == (0 if mode == "copies" else hr) and hr in (0, 1)
+    ref1 = t1.download()
+    _assert_entries(got, ref1, pairs, "first build")
+    t2.build()
+    got = _read_entries(t1, pairs)          # at once, through the table that has decided
+    ref2 = t2.download()
+    s, u = pairs[:, 0], pairs[:, 1]
+    assert (ref2["lat"][s, u] != ref1["lat"][s, u]).all()     # every record is new
+    _assert_entries(got, ref2, pairs, f"after the second build (host_reads={hr})")
+    # a device-side overwrite of 100 records by torch
+    e = torch.from_numpy(((s[:100] // 64) * t1.A + u[:100]) * 64 + s[:100] % 64).cuda()
+    assert len(set(e.tolist())) > 90
+    new_lr = torch.from_numpy(rng.uniform(100.0, 200.0, (100, 2))).cuda()
+    new_nx = torch.arange(7000, 7100, dtype=torch.int32, device="cuda")
+    new_hp = torch.arange(500, 600, dtype=torch.int16, device="cuda")
+    bufs[0][e] = new_lr
+    bufs[1][e] = new_nx
+    bufs[2][e] = new_hp
+    torch.cuda.synchronize()
+    ref3 = t2.download()
+    assert (ref3["lat"][s[:100], u[:100]] >= 100.0).all() and (ref3["hops"][s[:100], u[:100]] >= 500).all()
+    _assert_entries(_read_entries(t1, pairs), ref3, pairs, f"after the device-side overwrite (host_reads={hr})")
+    t3 = spe.PathTable(g1, A, ext=ptrs, ext_filled=True)
+    _assert_entries(_read_entries(t3, pairs), ref3, pairs, "adopted after the overwrite")
+    print(f"mode {mode}: adopted table host_reads={t3.layout()['host_reads']}")
+    for t in (t1, t2, t3):
+        t.close()
+
+
 def test_host_reads_on_a_block_range_table(spe):
     """A table owning blocks [2, 5) of the sources: offsets are block-relative."""
     top = graphs.gen_random_small(800, 2400, 12)
