@@ -194,6 +194,12 @@ typedef struct spe_table_opts {
      * allows 1e-9), exact where every weight is k / 2^q.  A source whose
      * anchor's parent decisions are within rounding of a tie is rebuilt on its own lane. */
     int32_t exact_sources;
+    /* 1: spe_table_build of a multi-device table ends with spe_table_verify_replicas (after the
+     * gather): spe_build_stats.replica_mismatches / verify_seconds are filled and the build
+     * returns SPE_ESTATE when some replica's records differ from the builder's (spe_last_error
+     * names the first bad replica and block).  Default 0: nothing is digested.  Ignored by
+     * single-device tables (one replica: nothing to compare). */
+    int32_t verify_replicas;
 } spe_table_opts;
 
 #define SPE_RELAX_AUTO 0            /* the default below */
@@ -285,6 +291,10 @@ typedef struct spe_build_stats {
     int64_t derived_sources;        /* contracted shared tables: sources whose rows came from their
                                      * neighbours' roots (three for a contracted vertex, four for a
                                      * degree-4 one), without a relaxation lane */
+    int64_t replica_mismatches;     /* spe_table_opts.verify_replicas: spe_replica_report.mismatching_blocks
+                                     * of the build's verification; -1 = not checked */
+    double verify_seconds;          /* ... and its wall time (not part of seconds / gather_seconds);
+                                     * 0 = not checked */
 } spe_build_stats;
 
 const char* spe_last_error(void);
@@ -476,6 +486,73 @@ typedef struct spe_compare_report {
     int32_t first_bad_t;
 } spe_compare_report;
 int spe_table_compare(const spe_table* a, const spe_table* b, double rel_tol, spe_compare_report* out);
+
+/* Per-block table digests: 4 x 8 bytes per 64-source block that can be compared across
+ * devices, ranks, storage layouts and a host restatement, where copying the records
+ * (55 GB on C3, 160 GB on C4) cannot.  All arithmetic on uint64, wrapping mod 2^64:
+ *
+ *   mix(x):  x ^= x >> 30;  x *= 0xbf58476d1ce4e5b9;
+ *            x ^= x >> 27;  x *= 0x94d049bb133111eb;
+ *            x ^= x >> 31;  return x                  (the splitmix64 finaliser, a bijection)
+ *   key(s, t)     = s_slot * n_attached + t_slot      (global slots)
+ *   km(s, t)      = mix(key + 1)
+ *   term(f, s, t) = mix(bits_f(s, t) + km * (2 f + 1))
+ *   digest[b][f]  = sum of term(f, s, t) over s in [64 b, min(64 b + 64, n_attached)),
+ *                   t in [0, n_attached)
+ *
+ * with the fields f and their bits: 0 latency, the f64 bit pattern; 1 reliability, the f64
+ * bit pattern; 2 next hop, the int32 reinterpreted as uint32, zero-extended; 3 hop count,
+ * the uint16, zero-extended.
+ *   - The sum is commutative: any reduction order gives the same 64 bits, so the digest is
+ *     deterministic and needs no ordered pass.
+ *   - The key is the global (s, t), not the SB64 offset: the digest of block b is the same
+ *     for a whole table, a block-range table, caller-owned storage, a replica span and a
+ *     row-major download.
+ *   - For a fixed entry and field, term is a bijection of the bits: any single-entry change
+ *     always changes the digest; several changes cancel with probability 2^-64.
+ *   - Padding lanes of the last block (s >= n_attached) and padding blocks of a replica span
+ *     (b >= the block count) are never read into a digest (they hold whatever the storage
+ *     held before). */
+typedef struct spe_block_digest {
+    uint64_t latency;
+    uint64_t reliability;
+    uint64_t next_hop;
+    uint64_t hops;
+} spe_block_digest;
+/* Digests of the owned blocks [block_begin, block_end) of a built (or ext_filled) table,
+ * computed on the device, to a host array of block_end - block_begin elements.  A
+ * multi-device table answers from its home replica (spe_table_digest_replica, replica 0).
+ * SPE_EINVAL: NULL argument; block range empty, reversed or not owned.  SPE_ESTATE: some
+ * block of the range is not built (and the storage was not handed over ext_filled). */
+int spe_table_digest(const spe_table* t, int32_t block_begin, int32_t block_end, spe_block_digest* out);
+/* The same from replica `replica` of a multi-device table (0 = the home device; for a
+ * single-device table only 0): latency / reliability are digested from that replica's own
+ * record span, on its device and stream; next_hop / hops on the device that holds them for
+ * the block (the part spe_table_get reads: they are never replicated).  SPE_EINVAL also for
+ * a replica out of range. */
+int spe_table_digest_replica(const spe_table* t, int32_t replica, int32_t block_begin, int32_t block_end,
+                             spe_block_digest* out);
+/* Device pointer of replica `replica`'s {latency, reliability} span, on
+ * spe_table_replica_device's device (replica 0 = spe_table_layout.latrel). */
+int spe_table_replica_latrel(const spe_table* t, int32_t replica, void** latrel);
+/* Are the replicas the table?  Every replica of a built multi-device table digests the
+ * records of every real block on its own device (all devices concurrently, each on its own
+ * stream), and each block's digests are compared with the reference: the digests taken on
+ * the device that BUILT the block, or -- for the blocks every device builds itself
+ * (spe_table_opts.shared_fraction < 1) -- on the lowest replica: independent builds must
+ * agree bit for bit.  A single-device table answers replicas = 1 and no mismatch.
+ * first_bad_*: the lowest replica with a mismatch and its lowest such block.
+ * SPE_EINVAL: NULL argument or another struct_size; SPE_ESTATE: table not built. */
+typedef struct spe_replica_report {
+    uint32_t struct_size;           /* sizeof(spe_replica_report) as the caller compiled it */
+    int32_t replicas;
+    int32_t blocks;
+    int64_t mismatching_blocks;     /* (replica, block) pairs whose record digests differ from the builder's */
+    int32_t first_bad_replica;      /* -1 none */
+    int32_t first_bad_block;
+    double seconds;                 /* wall time of the verification */
+} spe_replica_report;
+int spe_table_verify_replicas(const spe_table* t, spe_replica_report* out);
 /* Minimum latency over every owned routable entry (minimumPathLatency). */
 /* On-disk path-table cache (the reference recomputes its paths
  * every run).  The key hashes everything that determines the rows: the graph

@@ -592,7 +592,91 @@ int spe_table_replica_device(const spe_table* t, int32_t replica, int32_t* devic
     return SPE_OK;
 }
 
+int spe_table_digest(const spe_table* t, int32_t block_begin, int32_t block_end, spe_block_digest* out) {
+    if (!t || !out) return fail(SPE_EINVAL, "NULL argument");
+    if (t->multi) return spe_table_digest_replica(t, 0, block_begin, block_end, out);
+    return spe::table_digest_fields(t, block_begin, block_end, 15u, out);
+}
+
+int spe_table_digest_replica(const spe_table* t, int32_t replica, int32_t block_begin, int32_t block_end,
+                             spe_block_digest* out) {
+    if (!t || !out) return fail(SPE_EINVAL, "NULL argument");
+    if (t->multi) {
+        if (!t->built) return fail(SPE_ESTATE, "table not built");
+        return spe::multi_digest(t->multi, replica, block_begin, block_end, out);
+    }
+    if (replica != 0) return fail(SPE_EINVAL, "a single-device table has one replica (0)");
+    return spe::table_digest_fields(t, block_begin, block_end, 15u, out);
+}
+
+int spe_table_replica_latrel(const spe_table* t, int32_t replica, void** latrel) {
+    if (!t || !latrel) return fail(SPE_EINVAL, "NULL argument");
+    if (t->multi) return spe::multi_replica_latrel(t->multi, replica, latrel);
+    if (replica != 0) return fail(SPE_EINVAL, "a single-device table has one replica (0)");
+    *latrel = t->tb.lr;
+    return SPE_OK;
+}
+
+int spe_table_verify_replicas(const spe_table* t, spe_replica_report* out) {
+    if (!t || !out) return fail(SPE_EINVAL, "NULL argument");
+    if (out->struct_size != sizeof(spe_replica_report)) return fail(SPE_EINVAL, ABI_MSG("spe_replica_report"));
+    if (!t->built) return fail(SPE_ESTATE, "table not built");
+    if (t->multi) return spe::multi_verify(t->multi, out);
+    out->replicas = 1;
+    out->blocks = t->blk1 - t->blk0;
+    out->mismatching_blocks = 0;
+    out->first_bad_replica = out->first_bad_block = -1;
+    out->seconds = 0.0;
+    return SPE_OK;
+}
+
 }  // extern "C"
+
+int spe::digest_span(int32_t device, void* stream, int32_t A, int32_t b0, int32_t nb, const void* latrel,
+                     const void* next_hop, const void* hops, uint32_t fields, uint64_t* d_out) {
+    uint32_t mask = fields & 15u;
+    if (!latrel) mask &= ~3u;
+    if (!next_hop) mask &= ~4u;
+    if (!hops) mask &= ~8u;
+    if (nb <= 0 || !mask) return SPE_OK;
+    HIP_TRY(hipSetDevice(device));
+    // one wave per (block, DG_TC targets) item; 2048 workgroups = every wave slot of the
+    // device (256 CUs x 32 waves), larger tables take further grid-stride passes
+    const int64_t items = (int64_t)nb * ((A + DG_TC - 1) / DG_TC);
+    k_table_digest<<<grid_for(items * WAVE, BLOCK, 2048), BLOCK, 0, (hipStream_t)stream>>>(
+        A, b0, nb, (const double2*)latrel, (const int32_t*)next_hop, (const uint16_t*)hops, mask,
+        (unsigned long long*)d_out);
+    HIP_TRY(hipGetLastError());
+    return SPE_OK;
+}
+
+int spe::table_digest_fields(const spe_table* t, int32_t block_begin, int32_t block_end, uint32_t fields,
+                             spe_block_digest* out) {
+    if (!t || !out || t->multi) return fail(SPE_EINVAL, "NULL argument");
+    if (block_begin < t->blk0 || block_end > t->blk1 || block_begin >= block_end)
+        return fail(SPE_EINVAL, "block range empty, reversed or not owned by this table");
+    for (int32_t b = block_begin; b < block_end; ++b)
+        if (!t->blk_built[(size_t)(b - t->blk0)]) return fail(SPE_ESTATE, "blocks not built");
+    static_assert(sizeof(spe_block_digest) == 4 * sizeof(uint64_t), "spe_block_digest is the kernel's out[block][4]");
+    HIP_TRY(hipSetDevice(t->g->device));
+    const int32_t nb = block_end - block_begin;
+    const size_t bytes = (size_t)nb * sizeof(spe_block_digest);
+    uint64_t* d = nullptr;
+    HIP_TRY(hipMalloc(&d, bytes));
+    const size_t off = (size_t)(block_begin - t->blk0) * t->A * WAVE;
+    hipError_t e = hipMemsetAsync(d, 0, bytes, t->stream);
+    int r = SPE_OK;
+    if (e == hipSuccess)
+        r = spe::digest_span(t->g->device, t->stream, t->A, block_begin, nb, t->tb.lr + off, t->tb.next + off,
+                             t->tb.hops + off, fields, d);
+    if (e == hipSuccess && !r) e = hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, t->stream);
+    const hipError_t es = hipStreamSynchronize(t->stream);   // also on an error: nothing may still write d
+    if (e == hipSuccess) e = es;
+    (void)hipFree(d);
+    if (r) return r;
+    if (e != hipSuccess) return fail(SPE_EHIP, std::string("spe_table_digest: ") + hipGetErrorString(e));
+    return SPE_OK;
+}
 
 int spe::lookup_on_replica(int32_t device, const void* latrel, int32_t A, int32_t nblk, const int32_t* d_pairs,
                            int64_t q, double* d_latency, double* d_reliability, uint8_t* d_ok, void* stream) {

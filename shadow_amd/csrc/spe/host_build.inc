@@ -860,6 +860,7 @@ static int build_blocks_impl(spe_table* t, int32_t block_begin, int32_t block_en
     const auto t0 = std::chrono::steady_clock::now();
     const spe_graph* g = t->g;
     t->stats = spe_build_stats{};
+    t->stats.replica_mismatches = -1;   // one device: nothing to verify
     const bool ovl = t->overlap && !t->md.complete && t->engine == SPE_ENGINE_BATCH;
     hipStream_t rs = ovl ? t->rows_stream : s;
     if (t->share && !t->share_off) {

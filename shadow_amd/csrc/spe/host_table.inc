@@ -214,6 +214,7 @@ int spe_table_create(spe_graph* g, const int32_t* attached, int32_t n_attached, 
         t->blk1 = o.block_end;
     }
     t->row_base = t->blk0;
+    t->stats.replica_mismatches = -1;   // not checked (spe_table_opts.verify_replicas)
     const bool force = o.force_sssp != 0;
     {   // table cache key: graph, attached set, and every option that changes a row
         Fnv f;

@@ -750,6 +750,78 @@ __global__ __launch_bounds__(BLOCK) void k_table_compare(int32_t A, int32_t blk0
     }
 }
 
+// Per-block table digests (spe_table_digest, include/spe.h states the definition):
+//   digest[b][f] = sum over s in block b (s < A), t in [0, A) of
+//                  mix(bits_f(s, t) + km(s, t) * (2 f + 1)),  km = mix(s * A + t + 1),
+// all on uint64 mod 2^64, mix = the splitmix64 finaliser.  The sum commutes, so the
+// 64 bits do not depend on which wave adds what when.
+//
+// An HBM stream: a work item is (block, chunk of DG_TC targets), one wave per item,
+// lane = source lane, one target per step -- the record load is the 1-KB SB64
+// segment (16 B per lane), the next hops 256 B, the hop counts 128 B.  Every lane
+// carries the four sums of its source; the item ends with a wave reduction (shuffles
+// of the 32-bit halves) and one 64-bit atomic add per field into out[block][f].
+// Lanes of the last block at or past A (padding: no source) load nothing and add 0.
+// All pointers address block b0's first element; `mask` bit f = field f is wanted
+// (a replica that holds only records: mask 3 costs only the record stream).
+constexpr int32_t DG_TC = 128;
+
+__device__ __forceinline__ unsigned long long dg_mix(unsigned long long x) {
+    x ^= x >> 30;
+    x *= 0xbf58476d1ce4e5b9ull;
+    x ^= x >> 27;
+    x *= 0x94d049bb133111ebull;
+    x ^= x >> 31;
+    return x;
+}
+
+__global__ __launch_bounds__(BLOCK) void k_table_digest(int32_t A, int32_t b0, int32_t nb,
+                                                        const double2* __restrict__ lr,
+                                                        const int32_t* __restrict__ nx,
+                                                        const uint16_t* __restrict__ hp, uint32_t mask,
+                                                        unsigned long long* __restrict__ out) {
+    const int32_t lane = threadIdx.x & (WAVE - 1);
+    const int32_t chunks = (A + DG_TC - 1) / DG_TC;
+    const int64_t items = (int64_t)nb * chunks;
+    const int64_t waves = (int64_t)gridDim.x * (BLOCK / WAVE);
+    const bool want_lr = (mask & 3u) != 0, want_nx = (mask & 4u) != 0, want_hp = (mask & 8u) != 0;
+    for (int64_t it = (int64_t)blockIdx.x * (BLOCK / WAVE) + threadIdx.x / WAVE; it < items; it += waves) {
+        const int32_t bl = (int32_t)(it / chunks);                     // wave-uniform
+        const int32_t t0 = (int32_t)(it - (int64_t)bl * chunks) * DG_TC;
+        const int32_t t1 = min(A, t0 + DG_TC);
+        const int32_t s = (b0 + bl) * WAVE + lane;
+        unsigned long long acc0 = 0, acc1 = 0, acc2 = 0, acc3 = 0;
+        if (s < A) {
+            unsigned long long key1 = (unsigned long long)s * (unsigned long long)A + (unsigned long long)t0 + 1ull;
+            size_t o = tidx(bl, A, t0, lane);
+#pragma unroll 4
+            for (int32_t t = t0; t < t1; ++t, ++key1, o += WAVE) {
+                const unsigned long long km = dg_mix(key1), k2 = km << 1;   // km once per pair
+                if (want_lr) {
+                    const double2 e = lr[o];
+                    acc0 += dg_mix((unsigned long long)__double_as_longlong(e.x) + km);
+                    acc1 += dg_mix((unsigned long long)__double_as_longlong(e.y) + km + k2);
+                }
+                if (want_nx) acc2 += dg_mix((unsigned long long)(uint32_t)nx[o] + km + k2 + k2);
+                if (want_hp) acc3 += dg_mix((unsigned long long)hp[o] + km + k2 + k2 + k2);
+            }
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            acc0 += __shfl_xor(acc0, off);
+            acc1 += __shfl_xor(acc1, off);
+            acc2 += __shfl_xor(acc2, off);
+            acc3 += __shfl_xor(acc3, off);
+        }
+        if (lane == 0) {
+            unsigned long long* d = out + (size_t)bl * 4;
+            if (mask & 1u) atomicAdd(d + 0, acc0);
+            if (mask & 2u) atomicAdd(d + 1, acc1);
+            if (want_nx) atomicAdd(d + 2, acc2);
+            if (want_hp) atomicAdd(d + 3, acc3);
+        }
+    }
+}
+
 // A system-scope release: the device caches write back what the table's kernels
 // wrote, so host loads through a large-BAR mapping see it (table_host_reads).
 __global__ void k_release_system() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, ""); }

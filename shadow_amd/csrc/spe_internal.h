@@ -114,6 +114,17 @@ int graph_clone(const spe_graph* g, int32_t device, spe_graph** out);
 int lookup_on_replica(int32_t device, const void* latrel, int32_t A, int32_t nblk, const int32_t* d_pairs,
                       int64_t q, double* d_latency, double* d_reliability, uint8_t* d_ok, void* stream);
 
+// k_table_digest over nb blocks of caller-described SB64 spans on `device`, enqueued on
+// `stream` (no synchronisation): every pointer addresses block b0's first element, a NULL
+// field is left out (its digests stay as d_out holds them), `fields` bit f = field f of
+// spe_block_digest is wanted.  The kernel ADDS into d_out (nb x 4 uint64 on the device),
+// which the caller zeroes on the same stream first.
+int digest_span(int32_t device, void* stream, int32_t A, int32_t b0, int32_t nb, const void* latrel,
+                const void* next_hop, const void* hops, uint32_t fields, uint64_t* d_out);
+// spe_table_digest of a single-device table restricted to `fields`; the others are 0
+int table_digest_fields(const spe_table* t, int32_t block_begin, int32_t block_end, uint32_t fields,
+                        spe_block_digest* out);
+
 // Multi-device tables (spe_multi.cpp): one part table per device over a
 // contiguous share of the 64-source blocks; the {latency, reliability}
 // records are then all-gathered so every device holds the whole table.
@@ -135,6 +146,9 @@ int multi_layout(const MultiDev* m, spe_table_layout* out);
 int multi_profile_enable(MultiDev* m, int32_t enable);
 int multi_profile_get(const MultiDev* m, spe_kernel_profile* out);
 int multi_source_tree(MultiDev* m, int32_t s_slot, int32_t* parent);
+int multi_digest(const MultiDev* m, int32_t replica, int32_t block_begin, int32_t block_end, spe_block_digest* out);
+int multi_replica_latrel(const MultiDev* m, int32_t replica, void** latrel);
+int multi_verify(const MultiDev* m, spe_replica_report* out);
 // The FW engine's closure buffers of one (part) table, for the multi-device
 // closure: pivot-row broadcast between devices, each device relaxing its own
 // row blocks (spe.hip fw_*; driven by spe_multi.cpp).

@@ -104,6 +104,7 @@ struct MultiDev {
     std::vector<ncclComm_t> comms;
     bool built = false;
     bool fw = false;                       // FW-engine parts: one closure across the devices
+    bool verify = false;                   // spe_table_opts.verify_replicas: multi_build ends with multi_verify
     spe_build_stats stats{};
 
     size_t blk_elems() const { return (size_t)A * kWave; }
@@ -137,6 +138,7 @@ int multi_create(spe_graph* g, const int32_t* attached, int32_t A, const spe_tab
     m->A = A;
     m->n = o.n_devices;
     m->devs.assign(o.devices, o.devices + o.n_devices);
+    m->verify = o.verify_replicas != 0;
     m->nblk = (A + kWave - 1) / kWave;
     // the split: FW parts share one closure over the shares, so they never split
     double x = 1.0;
@@ -215,6 +217,7 @@ int multi_create(spe_graph* g, const int32_t* attached, int32_t A, const spe_tab
         po.devices = nullptr;
         po.n_devices = 0;
         po.ext_filled = 0;
+        po.verify_replicas = 0;
         if (m->b1[d] > m->b0[d]) {
             po.block_begin = m->b0[d];
             po.block_end = m->b1[d];
@@ -565,10 +568,29 @@ int multi_build(MultiDev* m, spe_build_stats* stats) {
     s.gather = m->gather;
     s.shared_blocks = std::min(m->S, m->nblk);
     s.local_blocks = m->nblk - std::min(m->S, m->nblk);
+    s.replica_mismatches = -1;
+    m->built = true;
+    int r = SPE_OK;
+    if (m->verify) {   // after the gather, outside `seconds` and `gather_seconds`
+        spe_replica_report rep = SPE_STRUCT_INIT(spe_replica_report);
+        r = multi_verify(m, &rep);
+        if (!r) {
+            s.replica_mismatches = rep.mismatching_blocks;
+            s.verify_seconds = rep.seconds;
+            if (rep.mismatching_blocks > 0) {
+                m->built = false;
+                r = set_error(SPE_ESTATE, "replica verification: " + std::to_string(rep.mismatching_blocks) +
+                                              " (replica, block) record digests differ from the builder's, first replica " +
+                                              std::to_string(rep.first_bad_replica) + " block " +
+                                              std::to_string(rep.first_bad_block));
+            }
+        } else {
+            m->built = false;
+        }
+    }
     m->stats = s;
     if (stats) *stats = s;
-    m->built = true;
-    return SPE_OK;
+    return r;
 }
 
 bool multi_built(const MultiDev* m) { return m->built; }
@@ -611,6 +633,96 @@ int multi_download(const MultiDev* m, int32_t row_begin, int32_t row_end, double
         if (rc) return rc;
         r0 = r1;
     }
+    return SPE_OK;
+}
+
+// Record digests of blocks [bb, be) of every replica in `reps`, each on its own device and
+// gather stream, all enqueued before the first is waited for: out[i] takes be - bb elements.
+static int replica_record_digests(const MultiDev* m, const std::vector<int32_t>& reps, int32_t bb, int32_t be,
+                                  std::vector<std::vector<spe_block_digest>>* out) {
+    const int32_t nb = be - bb;
+    const size_t bytes = (size_t)nb * sizeof(spe_block_digest);
+    std::vector<uint64_t*> d(reps.size(), nullptr);
+    out->assign(reps.size(), std::vector<spe_block_digest>((size_t)nb));
+    int r = SPE_OK;
+    for (size_t i = 0; i < reps.size() && !r; ++i) {
+        const int32_t q = reps[i];
+        hipError_t e = hipSetDevice(m->devs[q]);
+        if (e == hipSuccess) e = hipMalloc(&d[i], bytes);
+        if (e == hipSuccess) e = hipMemsetAsync(d[i], 0, bytes, m->streams[q]);
+        if (e != hipSuccess) {
+            r = hip_fail("replica digests", e);
+            break;
+        }
+        r = digest_span(m->devs[q], m->streams[q], m->A, bb, nb, (const char*)m->replica[q] + (size_t)bb * m->blk_bytes(),
+                        nullptr, nullptr, 3u, d[i]);
+    }
+    for (size_t i = 0; i < reps.size(); ++i) {   // every started stream is drained, also on an error
+        if (!d[i]) continue;
+        const int32_t q = reps[i];
+        hipError_t e = hipSetDevice(m->devs[q]);
+        if (e == hipSuccess && !r) e = hipMemcpyAsync((*out)[i].data(), d[i], bytes, hipMemcpyDeviceToHost, m->streams[q]);
+        const hipError_t es = hipStreamSynchronize(m->streams[q]);
+        if (e == hipSuccess) e = es;
+        (void)hipFree(d[i]);
+        if (e != hipSuccess && !r) r = hip_fail("replica digests", e);
+    }
+    return r;
+}
+
+int multi_digest(const MultiDev* m, int32_t replica, int32_t block_begin, int32_t block_end, spe_block_digest* out) {
+    if (replica < 0 || replica >= m->n) return set_error(SPE_EINVAL, "replica out of range");
+    if (block_begin < 0 || block_end > m->nblk || block_begin >= block_end)
+        return set_error(SPE_EINVAL, "block range empty, reversed or not owned by this table");
+    std::vector<std::vector<spe_block_digest>> rec;
+    if (int r = replica_record_digests(m, {replica}, block_begin, block_end, &rec)) return r;
+    // next hops / hop counts: run by run from the part that holds them (what multi_get reads)
+    std::vector<spe_block_digest> nh((size_t)(block_end - block_begin));
+    for (int32_t b = block_begin; b < block_end;) {
+        int32_t run_end = 0;
+        const spe_table* p = part_of(m, b, &run_end);
+        const int32_t e = std::min(block_end, run_end);
+        if (int r = table_digest_fields(p, b, e, 12u, nh.data() + (b - block_begin))) return r;
+        b = e;
+    }
+    for (int32_t i = 0; i < block_end - block_begin; ++i) {
+        out[i].latency = rec[0][(size_t)i].latency;
+        out[i].reliability = rec[0][(size_t)i].reliability;
+        out[i].next_hop = nh[(size_t)i].next_hop;
+        out[i].hops = nh[(size_t)i].hops;
+    }
+    return SPE_OK;
+}
+
+int multi_replica_latrel(const MultiDev* m, int32_t replica, void** latrel) {
+    if (replica < 0 || replica >= m->n) return set_error(SPE_EINVAL, "replica out of range");
+    *latrel = m->replica[replica];
+    return SPE_OK;
+}
+
+int multi_verify(const MultiDev* m, spe_replica_report* out) {
+    if (!m->built) return set_error(SPE_ESTATE, "table not built");
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<int32_t> reps((size_t)m->n);
+    for (int32_t q = 0; q < m->n; ++q) reps[(size_t)q] = q;
+    std::vector<std::vector<spe_block_digest>> dg;
+    if (int r = replica_record_digests(m, reps, 0, m->nblk, &dg)) return r;
+    out->replicas = m->n;
+    out->blocks = m->nblk;
+    out->mismatching_blocks = 0;
+    out->first_bad_replica = out->first_bad_block = -1;
+    for (int32_t q = 0; q < m->n; ++q)
+        for (int32_t b = 0; b < m->nblk; ++b) {
+            // the reference: the device that built the block; every device built [S, nblk) itself
+            const int32_t ref = b < m->S ? b / m->cb : 0;
+            const spe_block_digest &x = dg[(size_t)q][(size_t)b], &y = dg[(size_t)ref][(size_t)b];
+            if (x.latency == y.latency && x.reliability == y.reliability) continue;
+            if (out->mismatching_blocks++ == 0) {
+                out->first_bad_replica = q;
+                out->first_bad_block = b;
+            }
+        }
+    out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return SPE_OK;
 }
 

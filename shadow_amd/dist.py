@@ -263,3 +263,50 @@ def rank_next_hop_slots(nblk: int, world: int, rank: int, sizes, S: int):
         out.append((l0, l1, slot))
         slot += l1 - l0
     return out, slot
+
+
+# ---- replica parity (include/spe.h spe_block_digest): after the gather every rank holds
+# the whole record span, and nothing else says that it holds the SAME records.  Each
+# rank digests the blocks it built (before the gather) and its whole gathered span
+# (after), PathTable.digest on an ext_filled table over its buffers; the digests --
+# 16 bytes per 64-source block -- are what is exchanged and compared here.
+
+def replica_parity(built, built_mask, gathered, dist) -> dict:
+    """Compare every rank's gathered records with the builders', by digest.
+
+    built       uint64 [nblk, 2]: the (latency, reliability) digests of the blocks this
+                rank built itself, taken from its build before the gather; rows where
+                built_mask is false are ignored
+    built_mask  bool [nblk]
+    gathered    uint64 [nblk, 2]: the digests of this rank's whole gathered record span
+
+    The three arrays are all-gathered (as int64 views); each block's reference is the
+    `built` digest of its lowest building rank.  Returns, identically on every rank,
+    {"ranks", "blocks", "mismatching_blocks": (rank, block) pairs whose gathered digest
+    differs from the reference, "first_bad": the lowest such rank and its lowest block,
+    or None, "unbuilt_blocks": blocks no rank claims (not compared)}.  Runs no GPU
+    work of its own."""
+    import torch
+    built = np.ascontiguousarray(built, np.uint64)
+    gathered = np.ascontiguousarray(gathered, np.uint64)
+    mask = np.ascontiguousarray(built_mask, bool)
+    nblk = mask.shape[0]
+    if built.shape != (nblk, 2) or gathered.shape != (nblk, 2):
+        raise ValueError("replica_parity: built and gathered are [blocks, 2], built_mask [blocks]")
+    world = dist.get_world_size()
+    dev = "cuda" if dist.get_backend() == "nccl" else "cpu"
+    mine = torch.from_numpy(np.concatenate([built.view(np.int64).ravel(), gathered.view(np.int64).ravel(),
+                                            mask.astype(np.int64)])).to(dev)
+    parts = [torch.empty_like(mine) for _ in range(world)]
+    dist.all_gather(parts, mine)
+    al = np.stack([p.cpu().numpy() for p in parts])            # [world, 5 nblk]
+    b_all = al[:, :2 * nblk].reshape(world, nblk, 2)
+    g_all = al[:, 2 * nblk:4 * nblk].reshape(world, nblk, 2)
+    m_all = al[:, 4 * nblk:] != 0
+    claimed = m_all.any(axis=0)
+    first = m_all.argmax(axis=0)                                # the lowest building rank of a claimed block
+    ref = b_all[first, np.arange(nblk)]                         # [nblk, 2]
+    bad = (g_all != ref[None]).any(axis=2) & claimed[None]      # [world, nblk]
+    r, b = np.nonzero(bad)
+    return {"ranks": int(world), "blocks": int(nblk), "mismatching_blocks": int(bad.sum()),
+            "first_bad": (int(r[0]), int(b[0])) if r.size else None, "unbuilt_blocks": int((~claimed).sum())}

@@ -1235,9 +1235,14 @@ static int snap_build(Topology* top, const int32_t* att_in, int32_t A, int64_t b
         devs[ndev++] = (int32_t)d;
         p = (*end == ',') ? end + 1 : end;
     }
+    /* SHADOW_SPE_VERIFY_REPLICAS=1 (with a device list): after the gather every device digests
+     * its replica of the records and the digests are compared with the builders'
+     * (spe_table_opts.verify_replicas); a replica that differs fails the seal */
+    const char* vr = getenv("SHADOW_SPE_VERIFY_REPLICAS");
     if (ndev > 1) {
         o.devices = devs;
         o.n_devices = ndev;
+        o.verify_replicas = vr && *vr && strcmp(vr, "0") != 0;
     }
     /* SHADOW_SPE_ENGINE=1|2|3: ask for the batch / LDS / FW engine (SPE_ENGINE_*); an
      * engine the graph does not fit falls back to the library's choice */
@@ -1300,6 +1305,14 @@ static int snap_build(Topology* top, const int32_t* att_in, int32_t A, int64_t b
     if (timing) tp[np++] = now_s();   /* mirror allocation */
     if (rc == SPE_OK && !loaded) {
         rc = spe_table_build(s->table, NULL);
+        if (rc == SPE_OK && o.verify_replicas) {
+            spe_build_stats bs;
+            memset(&bs, 0, sizeof bs);
+            bs.struct_size = sizeof bs;
+            if (spe_table_build_stats(s->table, &bs) == SPE_OK)
+                tlog(top, LOG_MESSAGE, "path table verified: %d replicas of %d blocks agree with their builders "
+                                       "(%.3f s)", bs.n_devices, (A + 63) / 64, bs.verify_seconds);
+        }
         if (rc == SPE_OK && cpath[0] && spe_table_save(s->table, cpath) != SPE_OK)
             tlog(top, LOG_WARNING, "could not save the path table cache: %s", spe_last_error());
     }

@@ -78,7 +78,8 @@ class TableOpts(_Sized):
                 ("gather", C.c_int32), ("relax_kernel", C.c_int32), ("rows_in_flight", C.c_int32),
                 ("waves_per_simd", C.c_int32), ("no_overlap", C.c_int32), ("delta_ms", C.c_double),
                 ("trace", C.c_int32), ("shared_fraction", C.c_double), ("gather_gbps", C.c_double),
-                ("build_seconds_hint", C.c_double), ("no_contract", C.c_int32), ("exact_sources", C.c_int32)]
+                ("build_seconds_hint", C.c_double), ("no_contract", C.c_int32), ("exact_sources", C.c_int32),
+                ("verify_replicas", C.c_int32)]
 
 
 class TableLayout(_Sized):
@@ -123,7 +124,17 @@ class BuildStats(_Sized):
                 ("seconds", C.c_double), ("gather_seconds", C.c_double), ("n_devices", C.c_int32),
                 ("gather", C.c_int32), ("shared_blocks", C.c_int32), ("local_blocks", C.c_int32),
                 ("build_wait_seconds", C.c_double), ("relaxed_lanes", C.c_int64), ("fallback_blocks", C.c_int32),
-                ("derived_sources", C.c_int64)]
+                ("derived_sources", C.c_int64), ("replica_mismatches", C.c_int64), ("verify_seconds", C.c_double)]
+
+
+class BlockDigest(C.Structure):
+    _fields_ = [("latency", C.c_uint64), ("reliability", C.c_uint64), ("next_hop", C.c_uint64), ("hops", C.c_uint64)]
+
+
+class ReplicaReport(_Sized):
+    _fields_ = [("struct_size", C.c_uint32), ("replicas", C.c_int32), ("blocks", C.c_int32),
+                ("mismatching_blocks", C.c_int64), ("first_bad_replica", C.c_int32), ("first_bad_block", C.c_int32),
+                ("seconds", C.c_double)]
 
 
 # every symbol include/spe.h declares (tests/test_abi.py checks the export table)
@@ -138,7 +149,8 @@ EXPORTS = ["spe_last_error", "spe_device_count", "spe_graph_create", "spe_graph_
            "spe_graph_adjacent", "spe_device_shares", "spe_graph_edge", "spe_table_source_tree",
            "spe_device_split", "spe_lookup_batch_replica", "spe_table_replica_device", "spe_table_check",
            "spe_lookup_batch_host", "spe_table_compare", "spe_table_get_latrel",
-           "spe_table_get_row_latrel"]
+           "spe_table_get_row_latrel", "spe_table_digest", "spe_table_digest_replica", "spe_table_replica_latrel",
+           "spe_table_verify_replicas"]
 
 _lib = None
 
@@ -183,6 +195,10 @@ def lib():
         L.spe_lookup_batch_host.argtypes = [P, P, C.c_int64, P, P, P]
         L.spe_table_check.argtypes = [P, P]
         L.spe_table_compare.argtypes = [P, P, C.c_double, P]
+        L.spe_table_digest.argtypes = [P, C.c_int32, C.c_int32, P]
+        L.spe_table_digest_replica.argtypes = [P, C.c_int32, C.c_int32, C.c_int32, P]
+        L.spe_table_replica_latrel.argtypes = [P, C.c_int32, P]
+        L.spe_table_verify_replicas.argtypes = [P, P]
         L.spe_device_split.argtypes = [C.c_int32, C.c_int32, C.c_double, P, P, P]
         L.spe_table_min_latency.argtypes = [P, P]
         L.spe_table_key.argtypes = [P, P]
@@ -317,7 +333,8 @@ class PathTable:
                  gather: int = SPE_GATHER_AUTO, relax_kernel: int = 0, rows_in_flight: int = 0,
                  waves_per_simd: int = 0, no_overlap: Optional[bool] = None, delta_ms: Optional[float] = None,
                  shared_fraction: float = 0.0, gather_gbps: float = 0.0, build_seconds_hint: float = 0.0,
-                 no_contract: Optional[bool] = None, exact_sources: Optional[bool] = None):
+                 no_contract: Optional[bool] = None, exact_sources: Optional[bool] = None,
+                 verify_replicas: bool = False):
         self.graph = graph
         self.attached = np.ascontiguousarray(attached, np.int32)
         self.A = int(self.attached.shape[0])
@@ -353,6 +370,7 @@ class PathTable:
             o.shared_fraction = float(shared_fraction)
             o.gather_gbps = float(gather_gbps)
             o.build_seconds_hint = float(build_seconds_hint)
+            o.verify_replicas = int(bool(verify_replicas))
         if ext is not None:  # three device pointers (ints): latrel (2 x f64), next_hop (i32), hops (u16)
             o.ext_latrel, o.ext_next_hop, o.ext_hops = [int(x) for x in ext]
             o.ext_filled = int(bool(ext_filled))
@@ -481,6 +499,31 @@ class PathTable:
         r = CompareReport()
         _check(lib().spe_table_compare(self.h, other.h, float(rel_tol), C.byref(r)), "spe_table_compare")
         return {f: getattr(r, f) for f, _ in CompareReport._fields_ if f != "struct_size"}
+
+    def digest(self, b0: Optional[int] = None, b1: Optional[int] = None, replica: Optional[int] = None) -> np.ndarray:
+        """spe_table_digest(_replica): uint64 [blocks, 4] -- the (latency, reliability,
+        next hop, hops) digests of blocks [b0, b1) (default: the owned blocks)."""
+        lay = self.layout() if b0 is None or b1 is None else None
+        b0 = lay["block_begin"] if b0 is None else int(b0)
+        b1 = lay["block_end"] if b1 is None else int(b1)
+        out = np.zeros((max(0, b1 - b0), 4), np.uint64)
+        if replica is None:
+            _check(lib().spe_table_digest(self.h, b0, b1, _p(out)), "spe_table_digest")
+        else:
+            _check(lib().spe_table_digest_replica(self.h, int(replica), b0, b1, _p(out)), "spe_table_digest_replica")
+        return out
+
+    def replica_latrel(self, replica: int) -> int:
+        """spe_table_replica_latrel: device pointer of that replica's {latency, reliability} span."""
+        p = C.c_void_p()
+        _check(lib().spe_table_replica_latrel(self.h, int(replica), C.byref(p)), "spe_table_replica_latrel")
+        return int(p.value or 0)
+
+    def verify_replicas(self) -> dict:
+        """spe_table_verify_replicas: every replica's record digests against the builder's."""
+        r = ReplicaReport()
+        _check(lib().spe_table_verify_replicas(self.h, C.byref(r)), "spe_table_verify_replicas")
+        return {f: getattr(r, f) for f, _ in ReplicaReport._fields_ if f != "struct_size"}
 
     def replica_device(self, replica: int) -> int:
         d = C.c_int32(0)
