@@ -200,6 +200,27 @@ typedef struct spe_table_opts {
      * names the first bad replica and block).  Default 0: nothing is digested.  Ignored by
      * single-device tables (one replica: nothing to compare). */
     int32_t verify_replicas;
+    /* 1: delivery-exact default tables.  Shadow turns a latency into simulated time as
+     * ceil(latency_ms * 1e6) ns (shd-worker.c:244).  The build keeps the default (shared /
+     * derived) rows and then re-folds, in path order, every entry of an offset row whose
+     * latency lies within the summation error bound of an ns boundary
+     * (spe_delivery_near_boundary), so that after the build every routable entry's
+     * ceil(latency * 1e6) equals that of the exact_sources = 1 build of the same table, and
+     * every flagged entry's latency equals the exact build's bit for bit.  Reliability,
+     * next hop and hops are what the default build writes.  A 64-source block with more
+     * flagged entries than delivery_refold_max allows is rebuilt one lane per source; when
+     * every relaxation edge latency is itself on the ns grid (every path sum is then at a
+     * boundary) the table is created as with exact_sources = 1.  spe_build_stats.delivery_*
+     * say which happened.  Not combinable with owner_rank, want_aux or n_devices > 1
+     * (SPE_EUNSUPPORTED).  Accepted and without effect (all delivery_* = 0) with
+     * exact_sources = 1, on the LDS and FW engines, on DIRECT tables and on graphs with
+     * sums_exact.  Default 0: same kernels, same bits, same cache key as before. */
+    int32_t exact_delivery;
+    /* exact_delivery: the largest share of one 64-source block's 64 * n_attached entries
+     * that may be re-folded entry by entry; a block above it is rebuilt one lane per
+     * source.  In (0, 1]; 0 = the library default, 0.15 (measured).  The worklist
+     * takes delivery_refold_max * 16 B per table entry of device memory. */
+    double delivery_refold_max;
 } spe_table_opts;
 
 #define SPE_RELAX_AUTO 0            /* the default below */
@@ -295,7 +316,24 @@ typedef struct spe_build_stats {
                                      * of the build's verification; -1 = not checked */
     double verify_seconds;          /* ... and its wall time (not part of seconds / gather_seconds);
                                      * 0 = not checked */
+    /* spe_table_opts.exact_delivery (all 0 when it is off or without effect) */
+    int64_t delivery_flagged;       /* offset-row entries whose latency met spe_delivery_near_boundary,
+                                     * counted in full even where the block was rebuilt instead */
+    int64_t delivery_changed;       /* re-folded entries whose latency bits changed */
+    int32_t delivery_fallback;      /* 0 none; 1 every block took a lane per source because every
+                                     * relaxation edge latency is on the ns grid (decided on the host
+                                     * at create); 2 at least one block exceeded delivery_refold_max */
+    double delivery_seconds;        /* device time of the re-fold pass */
 } spe_build_stats;
+
+/* The boundary predicate of spe_table_opts.exact_delivery (host-only; the row kernels
+ * evaluate the same inline): with x = latency_ms * 1e6 and m = 4 (hops + 2) 2^-53 x,
+ * 1 iff |x - rint(x)| <= m.  The offset fold and the path-order fold of one path each
+ * make at most `hops` additions of non-negative terms with partial sums <= L, so the two
+ * latencies differ by at most 2 hops u L (u = 2^-53) to first order, and the product by
+ * 1e6 adds one rounding on each side: m is twice that bound.  Two latencies of one path
+ * whose ceil(. * 1e6) differ therefore both satisfy it. */
+int spe_delivery_near_boundary(double latency_ms, int32_t hops);
 
 const char* spe_last_error(void);
 int spe_device_count(int32_t* out);

@@ -194,6 +194,17 @@ struct Table {
 
 __device__ __forceinline__ bool has_attr(double x) { return !__builtin_isnan(x); }
 
+// spe_table_opts.exact_delivery: is ceil(latency * 1e6) -- the packet delay in ns,
+// shd-worker.c:244 -- within reach of the few ulps an offset row's fold may differ from
+// the path-order fold?  Both folds make at most `hops` additions of non-negative terms
+// with partial sums <= L: |L_a - L_e| <= 2 hops u L to first order (u = 2^-53), and the
+// product by 1e6 rounds once on each side; m is twice that bound (spe.h states it).
+__host__ __device__ __forceinline__ bool delivery_near_boundary(double latency_ms, int32_t hops) {
+    const double x = latency_ms * 1e6;
+    const double m = ((double)(4 * (hops + 2)) * 0x1p-53) * x;
+    return __builtin_fabs(x - __builtin_rint(x)) <= m;
+}
+
 __device__ __forceinline__ size_t tidx(int32_t sb_local, int32_t A, int32_t j, int32_t lane) {
     return ((size_t)sb_local * (size_t)A + (size_t)j) * WAVE + (size_t)lane;
 }

@@ -1082,8 +1082,13 @@ void spe_table_free(spe_table* t) {
     if (t->ev_relaxed) (void)hipEventDestroy(t->ev_relaxed);
     for (hipEvent_t e : t->ev_rows)
         if (e) (void)hipEventDestroy(e);
+    if (t->h_dl) (void)hipHostFree(t->h_dl);
+    for (hipEvent_t e : t->ev_dl)
+        if (e) (void)hipEventDestroy(e);
     delete t;
 }
+
+int spe_delivery_near_boundary(double latency_ms, int32_t hops) { return delivery_near_boundary(latency_ms, hops) ? 1 : 0; }
 
 }  // extern "C"
 

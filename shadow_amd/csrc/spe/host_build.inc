@@ -344,15 +344,34 @@ static void launch_rows_sssp(spe_table* t, int grid, int32_t blocks, int32_t sb0
 #endif
 static void launch_rows_shared(spe_table* t, int grid, int32_t blocks, int32_t sb0, hipStream_t s,
                                const int32_t* rsrc, const int2* rli, const double2* rwa, const int2* rng) {
+    const Deliv dv{t->d_dlcnt, t->d_dlwork, t->dl_cap};
     if (SPE_SHARED_ROWS_LDS && !t->cx) {   // (contracted targets read three rows: the gather kernel)
         const int64_t work = (int64_t)((blocks + RT_B - 1) / RT_B) * ((t->A + RT_T - 1) / RT_T);
         const int g = (int)std::max<int64_t>(1, std::min<int64_t>(work, 2048));
+        if (t->delivery) {   // flags the pendant sources' entries at an ns boundary
+            if (t->lanes == 128)
+                k_rows_shared_lds<128, true><<<g, BLOCK, 0, s>>>(t->bn, blocks, sb0, rsrc, t->d_slots, *t->bG, t->md,
+                                                                 t->st, t->tb, rli, rwa, rng, dv);
+            else
+                k_rows_shared_lds<64, true><<<g, BLOCK, 0, s>>>(t->bn, blocks, sb0, rsrc, t->d_slots, *t->bG, t->md,
+                                                                t->st, t->tb, rli, rwa, rng, dv);
+            return;
+        }
         if (t->lanes == 128)
             k_rows_shared_lds<128><<<g, BLOCK, 0, s>>>(t->bn, blocks, sb0, rsrc, t->d_slots, *t->bG, t->md, t->st,
                                                        t->tb, rli, rwa, rng);
         else
             k_rows_shared_lds<64><<<g, BLOCK, 0, s>>>(t->bn, blocks, sb0, rsrc, t->d_slots, *t->bG, t->md, t->st,
                                                       t->tb, rli, rwa, rng);
+        return;
+    }
+    if (t->delivery) {
+        if (t->lanes == 128)
+            k_rows_sssp<128, false, true, true><<<grid, BLOCK, 0, s>>>(t->bn, blocks, sb0, rsrc, t->d_slots, *t->bG,
+                                                                        t->md, t->st, t->tb, rli, rwa, dv);
+        else
+            k_rows_sssp<64, false, true, true><<<grid, BLOCK, 0, s>>>(t->bn, blocks, sb0, rsrc, t->d_slots, *t->bG,
+                                                                       t->md, t->st, t->tb, rli, rwa, dv);
         return;
     }
     if (t->lanes == 128)
@@ -729,6 +748,10 @@ static int build_shared(spe_table* t, int32_t block_begin, int32_t block_end, hi
                 }
         }
         const int32_t sb0 = b - t->row_base;
+        const Deliv dv{t->d_dlcnt, t->d_dlwork, t->dl_cap};
+        if (t->delivery) {
+            HIP_TRY(hipMemsetAsync(t->d_dlcnt, 0, sizeof(uint32_t) * 2 * (size_t)nblk, s));
+        }
         {
             LaunchTimer lt(t, s, SPE_K_ROWS);
             if (t->derive) {
@@ -755,7 +778,21 @@ static int build_shared(spe_table* t, int32_t block_begin, int32_t block_end, hi
                         t->d_xrt, *t->bG, t->d_rorig, sh.exact ? 0 : 1, sh.wmin, sh.omax, hmax);
                     const int64_t ritems = (int64_t)nblk * ((t->A + LM_T - 1) / LM_T);
                     const int rgrid = (int)((std::min<int64_t>(ritems, 8192) + 7) & ~(int64_t)7);
-                    if (t->pend_targets) {
+                    if (t->delivery) {   // the same rows, entries at an ns boundary flagged for the re-fold
+                        if (t->pend_targets)
+                            k_rows_lm<true, true><<<rgrid, BLOCK, 0, s>>>(nblk, sb0, d_rsrc, t->d_slots, *t->bG, t->md,
+                                                                          t->tb, d_rli, t->d_der, t->d_xd, t->d_xrt,
+                                                                          sh.wmin, sh.omax, hmax, sh.exact ? 1 : 0,
+                                                                          t->d_sunsafe, dv);
+                        else
+                            k_rows_lm<false, true><<<rgrid, BLOCK, 0, s>>>(nblk, sb0, d_rsrc, t->d_slots, *t->bG, t->md,
+                                                                           t->tb, d_rli, t->d_der, t->d_xd, t->d_xrt,
+                                                                           sh.wmin, sh.omax, hmax, sh.exact ? 1 : 0,
+                                                                           t->d_sunsafe, dv);
+                        if (!t->pend_targets)
+                            k_rows_self<<<(nblk * WAVE + BLOCK - 1) / BLOCK, BLOCK, 0, s>>>(nblk, sb0, b * WAVE, d_rsrc,
+                                                                                           *t->bG, t->md, t->tb);
+                    } else if (t->pend_targets) {
                         k_rows_lm<true><<<rgrid, BLOCK, 0, s>>>(nblk, sb0, d_rsrc, t->d_slots, *t->bG, t->md, t->tb,
                                                                 d_rli, t->d_der, t->d_xd, t->d_xrt, sh.wmin, sh.omax,
                                                                 hmax, sh.exact ? 1 : 0, t->d_sunsafe);
@@ -781,6 +818,19 @@ static int build_shared(spe_table* t, int32_t block_begin, int32_t block_end, hi
                 launch_rows_shared(t, grid_for((int64_t)nblk * t->A * WAVE, BLOCK, 8192), nblk, sb0, s, d_rsrc,
                                    d_rli, d_rwa, d_rng);
             }
+            if (t->delivery) {
+                // the re-fold walks this batch's state: after its rows, before the next batch's
+                // relaxation (same stream) and before the direct-edge overlay
+                HIP_TRY(hipEventRecord(t->ev_dl[0], s));
+                const int rgrid = grid_for((int64_t)nblk * t->dl_cap, BLOCK, 2048);
+                if (L == 128)
+                    k_refold_delivery<128><<<rgrid, BLOCK, 0, s>>>(t->bn, nblk, sb0, t->d_slots, *t->bG, t->st, t->tb,
+                                                                   t->d_der, d_rwa, dv, t->d_dlcnt + nblk);
+                else
+                    k_refold_delivery<64><<<rgrid, BLOCK, 0, s>>>(t->bn, nblk, sb0, t->d_slots, *t->bG, t->st, t->tb,
+                                                                  t->d_der, d_rwa, dv, t->d_dlcnt + nblk);
+                HIP_TRY(hipEventRecord(t->ev_dl[1], s));
+            }
         }
         if (t->md.prefer) {
             LaunchTimer lt(t, s, SPE_K_DIRECT);
@@ -789,6 +839,9 @@ static int build_shared(spe_table* t, int32_t block_begin, int32_t block_end, hi
         }
         HIP_TRY(hipGetLastError());
         bool any_sunsafe = false;
+        const size_t deferred0 = deferred.size();
+        if (t->delivery)
+            HIP_TRY(hipMemcpyAsync(t->h_dl, t->d_dlcnt, sizeof(uint32_t) * 2 * (size_t)nblk, hipMemcpyDeviceToHost, s));
         if (t->derive) {
             HIP_TRY(hipMemcpyAsync(t->h_sunsafe, t->d_sunsafe, ns, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
@@ -818,6 +871,25 @@ static int build_shared(spe_table* t, int32_t block_begin, int32_t block_end, hi
                         break;
                     }
                 }
+        if (t->delivery) {
+            // flagged entries count in full; a block over its cap joins the blocks rebuilt one lane
+            // per source; changes count where the re-fold is what the block keeps
+            HIP_TRY(hipStreamSynchronize(s));
+            float ms = 0.f;
+            HIP_TRY(hipEventElapsedTime(&ms, t->ev_dl[0], t->ev_dl[1]));
+            t->stats.delivery_seconds += 1e-3 * (double)ms;
+            std::vector<uint8_t> rebuilt((size_t)nblk, 0);
+            for (size_t i = deferred0; i < deferred.size(); ++i) rebuilt[(size_t)(deferred[i] - b)] = 1;
+            for (int32_t k = 0; k < nblk; ++k) {
+                t->stats.delivery_flagged += t->h_dl[k];
+                if (t->h_dl[k] > (uint32_t)t->dl_cap) {
+                    t->stats.delivery_fallback = 2;
+                    if (!rebuilt[(size_t)k]) deferred.push_back(b + k);
+                } else if (!rebuilt[(size_t)k]) {
+                    t->stats.delivery_changed += t->h_dl[nblk + k];
+                }
+            }
+        }
         if (t->prof) {
             HIP_TRY(hipStreamSynchronize(s));
             r = resolve_profile(t, true);
@@ -861,6 +933,7 @@ static int build_blocks_impl(spe_table* t, int32_t block_begin, int32_t block_en
     const spe_graph* g = t->g;
     t->stats = spe_build_stats{};
     t->stats.replica_mismatches = -1;   // one device: nothing to verify
+    t->stats.delivery_fallback = t->dl_fallback;
     const bool ovl = t->overlap && !t->md.complete && t->engine == SPE_ENGINE_BATCH;
     hipStream_t rs = ovl ? t->rows_stream : s;
     if (t->share && !t->share_off) {
@@ -1021,8 +1094,8 @@ int spe_table_profile_get(const spe_table* t, spe_kernel_profile* out) {
 }
 
 int spe_table_build_stats(const spe_table* t, spe_build_stats* out) {
+    if (out && out->struct_size != sizeof(spe_build_stats)) return fail(SPE_EINVAL, ABI_MSG("spe_build_stats"));
     if (!t || !out) return fail(SPE_EINVAL, "NULL argument");
-    if (out->struct_size != sizeof(spe_build_stats)) return fail(SPE_EINVAL, ABI_MSG("spe_build_stats"));
     *out = t->stats;
     out->struct_size = sizeof(spe_build_stats);
     return SPE_OK;

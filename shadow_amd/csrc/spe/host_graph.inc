@@ -134,6 +134,14 @@ struct spe_table {
     int32_t nr = 0;
     uint8_t* h_sunsafe = nullptr;
     bool derive = false;           // contracted sources take their neighbours' roots (no lane)
+    // spe_table_opts.exact_delivery (DESIGN §4.1): flagged entries of the shared rows are re-folded
+    bool delivery = false;         // the shared build flags and re-folds
+    int32_t dl_fallback = 0;       // 1: every edge latency on the ns grid, created as exact_sources = 1
+    int32_t dl_cap = 0;            // worklist records per 64-source block
+    uint32_t* d_dlcnt = nullptr;   // per block of the batch: flagged entries, then (k_refold_delivery) changed ones
+    int4* d_dlwork = nullptr;      // [owned blocks][dl_cap] records (Deliv)
+    uint32_t* h_dl = nullptr;      // pinned copy of both
+    hipEvent_t ev_dl[2] = {nullptr, nullptr};   // around the re-fold pass (delivery_seconds)
     // spe_lookup_batch_host / spe_table_get: device + pinned staging, grown on demand,
     // one caller at a time (the topology shim queries from several worker threads)
     struct HostLookup {

@@ -174,6 +174,8 @@ void spe_graph_free(spe_graph* g) {
 
 int spe_table_create(spe_graph* g, const int32_t* attached, int32_t n_attached, const spe_table_opts* opts,
                      spe_table** out) {
+    // (the ABI guard first: nothing else of a caller built against another spe.h is read)
+    if (opts && opts->struct_size != sizeof(spe_table_opts)) return fail(SPE_EINVAL, ABI_MSG("spe_table_opts"));
     if (!g || !attached || n_attached <= 0 || !out) return fail(SPE_EINVAL, "spe_table_create: bad arguments");
     *out = nullptr;
     HIP_TRY(hipSetDevice(g->device));
@@ -203,6 +205,13 @@ int spe_table_create(spe_graph* g, const int32_t* attached, int32_t n_attached, 
     if ((o.ext_latrel || o.ext_next_hop || o.ext_hops) && !(o.ext_latrel && o.ext_next_hop && o.ext_hops))
         return fail(SPE_EINVAL, "external storage needs all three fields");
     if (o.devices && o.n_devices < 1) return fail(SPE_EINVAL, "n_devices must be >= 1 with a device list");
+    if (o.exact_delivery) {
+        if (o.owner_rank) return fail(SPE_EUNSUPPORTED, "exact_delivery is not combinable with owner_rank");
+        if (o.want_aux) return fail(SPE_EUNSUPPORTED, "exact_delivery is not combinable with want_aux");
+        if (o.n_devices > 1) return fail(SPE_EUNSUPPORTED, "exact_delivery is not combinable with n_devices > 1");
+        if (!(o.delivery_refold_max >= 0.0 && o.delivery_refold_max <= 1.0))
+            return fail(SPE_EINVAL, "delivery_refold_max must lie in (0, 1] (0 = the default)");
+    }
     auto* t = new spe_table();
     t->g = g;
     t->A = n_attached;
@@ -235,6 +244,10 @@ int spe_table_create(spe_graph* g, const int32_t* attached, int32_t n_attached, 
         const int32_t exact_src = o.exact_sources != 0;   // shared anchor trees change the last bits
         f.val(exact_src);
         if (has_owner) f.add(o.owner_rank, (size_t)n_attached * sizeof(int32_t));
+        if (o.exact_delivery) {   // hashed only when set: every earlier key is unchanged
+            const char ed[] = "exact_delivery";
+            f.add(ed, sizeof(ed));
+        }
         t->key = f.h;
     }
     if (o.devices) {   // one process, several devices (spe_multi.cpp)
@@ -388,6 +401,31 @@ int spe_table_create(spe_graph* g, const int32_t* attached, int32_t n_attached, 
         }
         t->share = any;
     }
+    // exact_delivery acts on shared rows whose sums are not exact (elsewhere every latency
+    // already is the path-order fold).  Where every relaxation edge latency, pendant edges
+    // included, is itself at an ns boundary, every path sum is: no fix-up is cheaper than
+    // a lane per source, so the table is created as with exact_sources = 1.
+    if (o.exact_delivery && t->share && !g->hg.share.exact) {
+        const spe::HostGraph& h = g->hg;
+        bool grid = true;
+        for (size_t k = 0; k < h.iw.size() && grid; ++k) grid = delivery_near_boundary(h.iw[k], 1);
+        for (int32_t v = 0; v < h.n && grid; ++v)
+            if (h.core_id[(size_t)v] < 0 && h.anchor_core[(size_t)v] >= 0)
+                grid = delivery_near_boundary(h.fiw[(size_t)h.fiptr[(size_t)v]], 1);
+        if (grid) {
+            t->share = false;
+            t->dl_fallback = 1;
+        } else if (t->cx && !SPE_ROWS_LM) {
+            delete t;
+            return fail(SPE_EUNSUPPORTED, "exact_delivery needs the lane-major derived rows (built with SPE_ROWS_LM=0)");
+        } else {
+            t->delivery = true;
+            const double share_max = o.delivery_refold_max > 0.0 ? o.delivery_refold_max : DELIVERY_REFOLD_DEFAULT;
+            const double per_block = (double)WAVE * (double)n_attached;
+            t->dl_cap = (int32_t)std::min(std::min(per_block, 2.0e9), std::max(1.0, std::ceil(share_max * per_block)));
+        }
+    }
+    t->stats.delivery_fallback = t->dl_fallback;
     t->derive = t->share && t->cx;
     if (t->share && o.groups_per_launch <= 0) {
         // lane groups per batch for shared tables: every root of the owned range in one
@@ -606,6 +644,10 @@ int spe_table_create(spe_graph* g, const int32_t* attached, int32_t n_attached, 
             for (int32_t r = 0; r < t->nr; ++r) ro[(size_t)r] = h.corev[(size_t)h.cx.rcore[(size_t)r]];
             TRY(dev_upload(t->allocs, ro, &t->d_rorig));
         }
+        if (t->delivery) {   // the worklist: the sum of the block caps of the largest batch (every owned block)
+            TRY(dev_alloc(t->allocs, &t->d_dlcnt, 2 * (owned_slots / WAVE)));   // flagged, then changed
+            TRY(dev_alloc(t->allocs, &t->d_dlwork, owned_slots / WAVE * (size_t)t->dl_cap));
+        }
     }
 #undef TRY
     // every failure from here on releases what was allocated (spe_table_free)
@@ -627,6 +669,11 @@ int spe_table_create(spe_graph* g, const int32_t* attached, int32_t n_attached, 
         if (t->derive) {
             HTRY(hipHostMalloc((void**)&t->h_der, t->leg_cap * sizeof(DLeg), hipHostMallocDefault));
             HTRY(hipHostMalloc((void**)&t->h_sunsafe, owned_slots, hipHostMallocDefault));
+        }
+        if (t->delivery) {
+            HTRY(hipHostMalloc((void**)&t->h_dl, 2 * (owned_slots / WAVE) * sizeof(uint32_t), hipHostMallocDefault));
+            HTRY(hipEventCreate(&t->ev_dl[0]));
+            HTRY(hipEventCreate(&t->ev_dl[1]));
         }
     }
     HTRY(hipHostMalloc((void**)&t->h_counts, std::max<size_t>(64, (size_t)t->max_iters + 2) * sizeof(int32_t),

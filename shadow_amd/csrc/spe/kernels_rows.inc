@@ -108,6 +108,41 @@ __device__ double aux_fold(const DevGraph& G, const State& st, int32_t g, int32_
     return a;
 }
 
+// spe_table_opts.exact_delivery (DESIGN §4.1): the row kernels' DELIVERY = true
+// instantiations test every routable entry of an offset row (a source without a
+// relaxation lane of its own: a pruned pendant behind its anchor, a derived source
+// behind a leg) with delivery_near_boundary and append the flagged ones to their 64-source
+// block's worklist, which k_refold_delivery re-folds in path order.
+struct Deliv {
+    uint32_t* cnt;    // [block of the batch] flagged entries (keeps counting past the cap)
+    int4* work;       // [block of the batch][cap] {source slot of the batch, target slot, root state
+                      // lane, winning leg (index into the batch's legs) or -1: the pendant edge rwa[source]}
+    int32_t cap;      // records per block: ceil(delivery_refold_max * 64 * A)
+};
+// spe_table_opts.delivery_refold_max = 0: half the flagged share at which re-folding a block
+// entry by entry costs what rebuilding it one lane per source does (MEASUREMENTS.md)
+#ifndef SPE_DELIVERY_REFOLD_DEFAULT
+#define SPE_DELIVERY_REFOLD_DEFAULT 0.15
+#endif
+constexpr double DELIVERY_REFOLD_DEFAULT = SPE_DELIVERY_REFOLD_DEFAULT;
+
+// One flagged entry per lane, every lane of the wave in block b (wave-uniform call):
+// one atomic per wave takes the wave's positions, lanes below the cap store a record.
+__device__ __forceinline__ void deliv_push(const Deliv& dv, int32_t b, bool flag, int32_t src, int32_t jt,
+                                           int32_t root_lane, int32_t leg) {
+    const uint64_t m = __ballot(flag);
+    if (!m) return;
+    const int32_t lane = threadIdx.x & (WAVE - 1);
+    const int32_t leader = __builtin_ctzll(m);
+    int32_t base = 0;
+    if (lane == leader) base = (int32_t)atomicAdd(dv.cnt + b, (uint32_t)__builtin_popcountll(m));
+    base = __shfl(base, leader);
+    if (flag) {
+        const uint32_t pos = (uint32_t)base + (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull));
+        if (pos < (uint32_t)dv.cap) dv.work[(size_t)b * (size_t)dv.cap + pos] = make_int4(src, jt, root_lane, leg);
+    }
+}
+
 // State -> table rows.  One wave per (64-source block of the batch, target
 // slot): lane l = source b*64 + l, i.e. lane group b*(64/L) + l/L, lane l%L.
 #ifndef ROWS_ITEMS
@@ -119,13 +154,15 @@ __device__ double aux_fold(const DevGraph& G, const State& st, int32_t g, int32_
 // source's row is its anchor's with the edge folded in front (latency w + d,
 // reliability (f_s a) r, one more hop, first hop the anchor).
 // (Here only for contracted shared tables; plain ones take k_rows_shared_lds.)
-template <int L, bool AUX, bool SHARE = false>
+template <int L, bool AUX, bool SHARE = false, bool DELIVERY = false>
 __global__ __launch_bounds__(BLOCK) void k_rows_sssp(int32_t n, int32_t blocks, int32_t sb0,
                                                      const int32_t* __restrict__ srcv,
                                                      const SlotInfo* __restrict__ slots, DevGraph G,
                                                      RowMode md, State st, Table tb,
                                                      const int2* __restrict__ rli = nullptr,
-                                                     const double2* __restrict__ rwa = nullptr) {
+                                                     const double2* __restrict__ rwa = nullptr,
+                                                     Deliv dv = Deliv{nullptr, nullptr, 0}) {
+    static_assert(!DELIVERY || SHARE, "only shared rows carry an offset");
     const int32_t lane = threadIdx.x & (WAVE - 1);
     const int64_t items_all = (int64_t)blocks * tb.A;
     // XCD-contiguous slices (grid a multiple of 8; workgroups are dealt round-robin
@@ -314,6 +351,10 @@ __global__ __launch_bounds__(BLOCK) void k_rows_sssp(int32_t n, int32_t blocks, 
                     }
                 }
             }
+            if constexpr (DELIVERY) {   // a pendant source's routable entry: offset by its edge
+                const bool off = s >= 0 && t != s && x.ri.y >= 0 && x.dc < INF;
+                deliv_push(dv, b, off && delivery_near_boundary(Lt, H), b * WAVE + lane, jt, x.ri.x, -1);
+            }
             const size_t o = tidx(sb0 + b, tb.A, jt, lane);
             // the table is written once and not read during the build: stream it
             dvec2 e;
@@ -346,14 +387,15 @@ __global__ __launch_bounds__(BLOCK) void k_rows_sssp(int32_t n, int32_t blocks, 
 #endif
 constexpr int RT_B = SPE_RT_B, RT_T = SPE_RT_T, RT_R = 24 * SPE_RT_B;
 
-template <int L>
+template <int L, bool DELIVERY = false>
 __global__ __launch_bounds__(BLOCK) void k_rows_shared_lds(int32_t n, int32_t blocks, int32_t sb0,
                                                            const int32_t* __restrict__ srcv,
                                                            const SlotInfo* __restrict__ slots, DevGraph G,
                                                            RowMode md, State st, Table tb,
                                                            const int2* __restrict__ rli,
                                                            const double2* __restrict__ rwa,
-                                                           const int2* __restrict__ rng) {
+                                                           const int2* __restrict__ rng,
+                                                           Deliv dv = Deliv{nullptr, nullptr, 0}) {
     __shared__ double sD[RT_T][RT_R];
     __shared__ Route sR[RT_T][RT_R];
     const int32_t lane = threadIdx.x & (WAVE - 1);
@@ -396,6 +438,8 @@ __global__ __launch_bounds__(BLOCK) void k_rows_shared_lds(int32_t n, int32_t bl
                 const SlotInfo si = slots[jt];
                 double Lt = -1.0, R = -1.0;
                 int32_t N = -1, H = 0;
+                bool off = false;   // (DELIVERY) a routable entry of a pendant source
+                (void)off;
                 if (s >= 0) {
                     if (si.t == s) {
                         self_entry(G, md, s, Lt, R, N, H);
@@ -416,6 +460,7 @@ __global__ __launch_bounds__(BLOCK) void k_rows_shared_lds(int32_t n, int32_t bl
                                 rc.r = wa.y * rc.r;
                                 rc.h = rc.h + 1;
                                 rc.f = ri.y;
+                                if constexpr (DELIVERY) off = true;
                             }
                             double d = dc;
                             Route rt2 = rc;
@@ -432,6 +477,8 @@ __global__ __launch_bounds__(BLOCK) void k_rows_shared_lds(int32_t n, int32_t bl
                         }
                     }
                 }
+                if constexpr (DELIVERY)
+                    deliv_push(dv, b, off && delivery_near_boundary(Lt, H), b * WAVE + lane, jt, ri.x, -1);
                 const size_t o = tidx(sb0 + b, tb.A, jt, lane);
                 dvec2 e;
                 e.x = Lt;
@@ -991,13 +1038,14 @@ __device__ __forceinline__ DLeg shfl_leg(const DLeg& x, int32_t src) {
 #define SPE_LM_WPE 7
 #endif
 #define SPE_LM_ATTR __attribute__((amdgpu_waves_per_eu(SPE_LM_WPE)))
-template <bool GEN>
+template <bool GEN, bool DELIVERY = false>
 __global__ __launch_bounds__(BLOCK) SPE_LM_ATTR void k_rows_lm(int32_t blocks, int32_t sb0, const int32_t* __restrict__ srcv,
                                                    const SlotInfo* __restrict__ slots, DevGraph G, RowMode md, Table tb,
                                                    const int2* __restrict__ lrng, const DLeg* __restrict__ legs,
                                                    const double* __restrict__ XD, const Route* __restrict__ XRT,
                                                    double wmin, double omax, double hmax, int32_t exact,
-                                                   uint8_t* __restrict__ sunsafe) {
+                                                   uint8_t* __restrict__ sunsafe,
+                                                   Deliv dv = Deliv{nullptr, nullptr, 0}) {
     constexpr int T = LM_T, KL = SPE_LM_KL;
     constexpr int SPS = WAVE / T;                          // sources per wave step
     constexpr int SPW = WAVE / (BLOCK / WAVE);             // sources per wave (16)
@@ -1072,6 +1120,8 @@ __global__ __launch_bounds__(BLOCK) SPE_LM_ATTR void k_rows_lm(int32_t blocks, i
             double bo = INF, m2 = INF, wa = 1.0;
             bool tg = false;
             int32_t wref = -1, whi = -1;
+            int32_t wk = 0;   // (DELIVERY) the winning leg
+            (void)wk;
             for (int32_t k0 = 0; k0 < nlmax; k0 += KL) {   // wave-uniform
                 DLeg d[KL];
                 double x[KL];
@@ -1111,6 +1161,7 @@ __global__ __launch_bounds__(BLOCK) SPE_LM_ATTR void k_rows_lm(int32_t blocks, i
                     wref = better ? d[k].ref : wref;
                     wa = better ? d[k].a : wa;
                     whi = better ? d[k].hopinc : whi;
+                    if constexpr (DELIVERY) wk = better ? k0 + k : wk;
                 }
             }
             bool bad = false;
@@ -1144,6 +1195,10 @@ __global__ __launch_bounds__(BLOCK) SPE_LM_ATTR void k_rows_lm(int32_t blocks, i
                     N = rt.f;
                     H = rt.h;
                 }
+            }
+            if constexpr (DELIVERY) {   // a leg with a prefix reading a root lane: an offset entry
+                const bool off = tv && s >= 0 && sv.t != s && bo < INF && whi >= 0 && wref >= 0;
+                deliv_push(dv, b, off && delivery_near_boundary(Lt, H), sl + b * WAVE, t, wref, lr.x + wk);
             }
             dvec2 e;
             e.x = Lt;
@@ -1186,6 +1241,88 @@ __global__ __launch_bounds__(BLOCK) void k_rows_self(int32_t blocks, int32_t sb0
     tb.lr[o] = make_double2(Lt, R);
     tb.next[o] = N;
     tb.hops[o] = (uint16_t)(H > 65535 ? 65535 : H);
+}
+
+// spe_table_opts.exact_delivery: the path-order latency of every worklist record (one
+// lane per record), as the source's own relaxation lane would have summed it
+// (exact_sources = 1): from the winning leg's prefix -- fl(0 + w1), or fl(fl(0 + w1) +
+// w2) for a two-edge leg, which is DLeg.w / the pendant edge bit for bit -- every tree
+// entry from the root to the target's relaxation vertex as the relaxation offers it,
+// fl(fl(L + iw[k]) + xw2[k]) (xw2 absent or 0: one add), then a removed target's last
+// edge and a pendant target's edge.  The tree is the root lane's: its parent entries are
+// walked back from the target (up to 64 kept and folded forward, longer paths re-walk per
+// entry as aux_fold does).  Blocks over the cap are left alone: the host rebuilds them
+// one lane per source.  Only the latency is stored; changed[b] counts block b's bit changes.
+template <int L>
+__global__ __launch_bounds__(BLOCK) void k_refold_delivery(int32_t n, int32_t blocks, int32_t sb0,
+                                                           const SlotInfo* __restrict__ slots, DevGraph G, State st,
+                                                           Table tb, const DLeg* __restrict__ legs,
+                                                           const double2* __restrict__ rwa, Deliv dv,
+                                                           uint32_t* __restrict__ changed) {
+    constexpr int KMAX = 64;
+    const int64_t nth = (int64_t)gridDim.x * BLOCK;
+    const int64_t tid = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    for (int32_t b = 0; b < blocks; ++b) {
+        const uint32_t cnt = dv.cnt[b];
+        if (cnt > (uint32_t)dv.cap) continue;
+        uint32_t nch = 0;
+        for (int64_t p = tid; p < (int64_t)cnt; p += nth) {
+            const int4 rec = dv.work[(size_t)b * (size_t)dv.cap + (size_t)p];
+            const int32_t i = rec.x, jt = rec.y, sl = rec.z;
+            const SlotInfo si = slots[jt];
+            const int32_t g = sl / L, j = sl % L;
+            int32_t c = si.c;
+            double last = 0.0;   // a removed target: the edge from the neighbour its row takes
+            if (c < 0) {         // the best of its three neighbours (d, then d[u], then u), k_rows_sssp's rule
+                const int32_t r = -2 - c;
+                const double d0 = st.D[sidx<L>(g, n, G.rnb[3 * r], j)], d1 = st.D[sidx<L>(g, n, G.rnb[3 * r + 1], j)],
+                             d2 = st.D[sidx<L>(g, n, G.rnb[3 * r + 2], j)];
+                const double a0 = d0 + G.rw[3 * r], a1 = d1 + G.rw[3 * r + 1], a2 = d2 + G.rw[3 * r + 2];
+                int32_t q = d0 < INF ? 0 : -1;
+                double bd = d0 < INF ? a0 : INF, bu = d0;
+                const bool t1 = (d1 < INF) & ((a1 < bd) | ((a1 == bd) & (d1 < bu)));
+                q = t1 ? 1 : q;
+                bd = t1 ? a1 : bd;
+                bu = t1 ? d1 : bu;
+                const bool t2 = (d2 < INF) & ((a2 < bd) | ((a2 == bd) & (d2 < bu)));
+                q = t2 ? 2 : q;
+                if (q < 0) continue;   // (unroutable entries are never flagged)
+                c = G.rnb[3 * r + q];
+                last = G.rw[3 * r + q];
+            }
+            int32_t ks[KMAX];
+            int32_t nk = 0;
+            for (int32_t x = c; nk <= n;) {   // (a tree path has fewer than n entries)
+                const int32_t k = st.P[sidx<L>(g, n, x, j)];
+                if (k < 0) break;             // the root
+                if (nk < KMAX) ks[nk] = k;
+                ++nk;
+                x = G.icol[k];
+            }
+            double l = rec.w >= 0 ? legs[rec.w].w : rwa[i].x;
+            for (int32_t q = nk - 1; q >= 0; --q) {
+                int32_t k;
+                if (q < KMAX) {
+                    k = ks[q];
+                } else {   // entry q (0 = the last one, into c)
+                    int32_t x = c;
+                    for (int32_t r = 0; r < q; ++r) x = G.icol[st.P[sidx<L>(g, n, x, j)]];
+                    k = st.P[sidx<L>(g, n, x, j)];
+                }
+                l = l + G.iw[k];
+                if (G.xw2) l = l + G.xw2[k];
+            }
+            if (si.c < 0) l = l + last;
+            if (si.kt >= 0) l = l + si.pw;
+            if (l == 0) l = 1;   // shd-topology.c:1833-1837
+            double* e = reinterpret_cast<double*>(tb.lr + tidx(sb0 + (i >> 6), tb.A, jt, i & (WAVE - 1)));
+            if (__double_as_longlong(*e) != __double_as_longlong(l)) {
+                *e = l;
+                ++nch;
+            }
+        }
+        if (nch) atomicAdd(changed + b, nch);
+    }
 }
 
 // Shared anchor trees: after a batch's relaxation over its roots, flag every root

@@ -1262,7 +1262,24 @@ static int snap_build(Topology* top, const int32_t* att_in, int32_t A, int64_t b
      * overrides it either way. */
     const char* ex = getenv("SHADOW_SPE_EXACT_SOURCES");
     o.exact_sources = top->shared_rows_exact ? 0 : 1;
-    if (ex && *ex) o.exact_sources = strcmp(ex, "0") != 0;
+    /* SHADOW_SPE_EXACT_DELIVERY=1: the default (shared / derived) rows with every latency
+     * at an ns boundary re-folded in path order (spe_table_opts.exact_delivery): the
+     * packet delays of the exact build at the default build's speed where the weights
+     * allow it.  An explicit SHADOW_SPE_EXACT_SOURCES still wins. */
+    const char* ed = getenv("SHADOW_SPE_EXACT_DELIVERY");
+    if (ed && *ed && strcmp(ed, "0") != 0) {
+        o.exact_sources = 0;
+        o.exact_delivery = 1;
+    }
+    if (ex && *ex) {
+        o.exact_sources = strcmp(ex, "0") != 0;
+        if (o.exact_sources) o.exact_delivery = 0;
+    }
+    if (o.exact_delivery && ndev > 1) {   /* single-device tables only: the default seal */
+        tlog(top, LOG_WARNING, "SHADOW_SPE_EXACT_DELIVERY is ignored with SHADOW_SPE_DEVICES (exact sources instead)");
+        o.exact_delivery = 0;
+        o.exact_sources = top->shared_rows_exact ? 0 : 1;
+    }
     if (timing) tp[np++] = now_s();   /* slot order */
     int rc = spe_table_create(top->graph, s->attached, A, &o, &s->table);
     if (rc == SPE_EUNSUPPORTED && o.engine != SPE_ENGINE_AUTO) {
@@ -1312,6 +1329,15 @@ static int snap_build(Topology* top, const int32_t* att_in, int32_t A, int64_t b
             if (spe_table_build_stats(s->table, &bs) == SPE_OK)
                 tlog(top, LOG_MESSAGE, "path table verified: %d replicas of %d blocks agree with their builders "
                                        "(%.3f s)", bs.n_devices, (A + 63) / 64, bs.verify_seconds);
+        }
+        if (rc == SPE_OK && o.exact_delivery) {
+            spe_build_stats bs;
+            memset(&bs, 0, sizeof bs);
+            bs.struct_size = sizeof bs;
+            if (spe_table_build_stats(s->table, &bs) == SPE_OK)
+                tlog(top, LOG_MESSAGE, "path table exact delivery: delivery_flagged %lld delivery_changed %lld "
+                                       "delivery_fallback %d delivery_seconds %.6f", (long long)bs.delivery_flagged,
+                     (long long)bs.delivery_changed, bs.delivery_fallback, bs.delivery_seconds);
         }
         if (rc == SPE_OK && cpath[0] && spe_table_save(s->table, cpath) != SPE_OK)
             tlog(top, LOG_WARNING, "could not save the path table cache: %s", spe_last_error());

@@ -79,7 +79,7 @@ class TableOpts(_Sized):
                 ("waves_per_simd", C.c_int32), ("no_overlap", C.c_int32), ("delta_ms", C.c_double),
                 ("trace", C.c_int32), ("shared_fraction", C.c_double), ("gather_gbps", C.c_double),
                 ("build_seconds_hint", C.c_double), ("no_contract", C.c_int32), ("exact_sources", C.c_int32),
-                ("verify_replicas", C.c_int32)]
+                ("verify_replicas", C.c_int32), ("exact_delivery", C.c_int32), ("delivery_refold_max", C.c_double)]
 
 
 class TableLayout(_Sized):
@@ -124,7 +124,9 @@ class BuildStats(_Sized):
                 ("seconds", C.c_double), ("gather_seconds", C.c_double), ("n_devices", C.c_int32),
                 ("gather", C.c_int32), ("shared_blocks", C.c_int32), ("local_blocks", C.c_int32),
                 ("build_wait_seconds", C.c_double), ("relaxed_lanes", C.c_int64), ("fallback_blocks", C.c_int32),
-                ("derived_sources", C.c_int64), ("replica_mismatches", C.c_int64), ("verify_seconds", C.c_double)]
+                ("derived_sources", C.c_int64), ("replica_mismatches", C.c_int64), ("verify_seconds", C.c_double),
+                ("delivery_flagged", C.c_int64), ("delivery_changed", C.c_int64), ("delivery_fallback", C.c_int32),
+                ("delivery_seconds", C.c_double)]
 
 
 class BlockDigest(C.Structure):
@@ -150,7 +152,7 @@ EXPORTS = ["spe_last_error", "spe_device_count", "spe_graph_create", "spe_graph_
            "spe_device_split", "spe_lookup_batch_replica", "spe_table_replica_device", "spe_table_check",
            "spe_lookup_batch_host", "spe_table_compare", "spe_table_get_latrel",
            "spe_table_get_row_latrel", "spe_table_digest", "spe_table_digest_replica", "spe_table_replica_latrel",
-           "spe_table_verify_replicas"]
+           "spe_table_verify_replicas", "spe_delivery_near_boundary"]
 
 _lib = None
 
@@ -215,6 +217,7 @@ def lib():
         L.spe_graph_adjacent.argtypes = [P, C.c_int32, C.c_int32, P]
         L.spe_graph_edge.argtypes = [P, C.c_int32, C.c_int32, P, P]
         L.spe_table_source_tree.argtypes = [P, C.c_int32, P]
+        L.spe_delivery_near_boundary.argtypes = [C.c_double, C.c_int32]
         _lib = L
     return _lib
 
@@ -247,6 +250,12 @@ def device_split(n_attached: int, n_devices: int, shared_fraction: float):
     _check(lib().spe_device_split(int(n_attached), int(n_devices), float(shared_fraction), _p(b0), _p(b1),
                                   C.byref(lb)), "spe_device_split")
     return list(zip(b0.tolist(), b1.tolist())), int(lb.value)
+
+
+def delivery_near_boundary(latency_ms: float, hops: int) -> bool:
+    """spe_delivery_near_boundary: is ceil(latency_ms * 1e6) within the summation error
+    bound of a `hops`-edge path of flipping (the exact_delivery predicate; host-only)."""
+    return bool(lib().spe_delivery_near_boundary(float(latency_ms), int(hops)))
 
 
 def device_count() -> int:
@@ -334,7 +343,7 @@ class PathTable:
                  waves_per_simd: int = 0, no_overlap: Optional[bool] = None, delta_ms: Optional[float] = None,
                  shared_fraction: float = 0.0, gather_gbps: float = 0.0, build_seconds_hint: float = 0.0,
                  no_contract: Optional[bool] = None, exact_sources: Optional[bool] = None,
-                 verify_replicas: bool = False):
+                 verify_replicas: bool = False, exact_delivery: bool = False, delivery_refold_max: float = 0.0):
         self.graph = graph
         self.attached = np.ascontiguousarray(attached, np.int32)
         self.A = int(self.attached.shape[0])
@@ -353,6 +362,8 @@ class PathTable:
         o.trace = _env_int("SPE_TRACE")
         o.no_contract = int(bool(no_contract if no_contract is not None else _env_int("SPE_NO_CONTRACT")))
         o.exact_sources = int(bool(exact_sources if exact_sources is not None else _env_int("SPE_EXACT_SOURCES")))
+        o.exact_delivery = int(bool(exact_delivery))
+        o.delivery_refold_max = float(delivery_refold_max)
         env_engine = engine == SPE_ENGINE_AUTO and not want_aux and _env_int("SPE_ENGINE") != 0
         if env_engine:
             o.engine = _env_int("SPE_ENGINE")
